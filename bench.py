@@ -16,6 +16,10 @@ Rank 0 prints ONE JSON line.  `models` holds the model-level legs of BASELINE.js
 
 Without a GPU (`--dry-run`, implied when torch.cuda is unavailable) only the launcher, the rendezvous,
 the barrier / max-over-ranks timing and the all-reduce probe run, on gloo: the product has no CPU path.
+
+`--dump-outputs DIR` writes what the last of the K timed steps returned -- `output`, `input_grad` (the same seeded
+sample of DUMP_SAMPLE positions of each) and `shift_grad` -- as DIR/<name>.npy in fp32.  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -34,22 +38,24 @@ from rubiksnet_amd import dp, rubiksnet_cuda  # noqa: E402
 SHAPE = (32, 8, 64, 56, 56)          # N, T, C, H, W
 HBM_PEAK_GBS = 8000.0                # MI355X HBM3E spec (MI355X_MICROARCH.md); 6290 measured copy ceiling
 COPY_CEILING_GBS = 6290.0
+DUMP_SAMPLE = 1 << 22                # elements kept of each [N,T,C,H,W] output by --dump-outputs (16 MB as fp32)
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def op_bench(env, steps, warmup, nsets=4, settle_s=0.4):
+def op_bench(env, steps, warmup, nsets=4, settle_s=0.4, dump=False):
     dev = env.device
     N, T, C, H, W = SHAPE
     numel = N * T * C * H * W
     g = torch.Generator(device="cpu").manual_seed(0)
     shift = (torch.rand(3, C, generator=g) * 2 - 1).to(dev)
+    gd = torch.Generator(device=dev).manual_seed(1)   # seeded: the same inputs in every run, whatever ran before
     sets = []
     for _ in range(nsets):   # rotate buffer sets: one 205 MB tensor fits the 256 MiB Infinity Cache
-        x = torch.empty(SHAPE, device=dev).uniform_(-1, 1)
-        gy = torch.empty(SHAPE, device=dev).uniform_(-1, 1)
+        x = torch.empty(SHAPE, device=dev).uniform_(-1, 1, generator=gd)
+        gy = torch.empty(SHAPE, device=dev).uniform_(-1, 1, generator=gd)
         sets.append((x, gy, torch.empty_like(x), torch.empty_like(x)))
     gshift = torch.empty(3, C, device=dev)
     s1, p0 = [1, 1, 1], [0, 0, 0]
@@ -82,6 +88,14 @@ def op_bench(env, steps, warmup, nsets=4, settle_s=0.4):
     # HIP events on the launch stream: event records between the kernels of a step cost ~15 us/step of marker
     # packets and idle gaps (tools/launch_gap_probe.py), which also changes the clock regime being measured.
     elapsed = dp.timed_region(env, lambda: step(False), steps)
+    outputs = None
+    if dump:   # what the LAST timed step handed its caller, read before the kernel passes below overwrite it
+        last = it[0] - 1
+        y, gx = sets[last % nsets][2], sets[(last + 2) % nsets][3]
+        rng = torch.Generator(device="cpu").manual_seed(2)
+        idx = torch.randperm(numel, generator=rng)[:DUMP_SAMPLE].sort().values.to(dev)
+        outputs = {"output": y.view(-1)[idx].cpu().numpy(), "input_grad": gx.view(-1)[idx].cpu().numpy(),
+                   "shift_grad": gshift.cpu().numpy()}
 
     def kernel_pass(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -131,8 +145,20 @@ def op_bench(env, steps, warmup, nsets=4, settle_s=0.4):
     return {
         "elapsed_s": elapsed, "numel": numel, "fwd_ms": fwd_ms, "bwd_ms": bwd_ms, "bwd_kernel_ms": bwd_kernel_ms,
         "finalize_ms": finalize_ms,
-        "bytes_fwd": 8 * numel, "bytes_bwd": 12 * numel,
+        "bytes_fwd": 8 * numel, "bytes_bwd": 12 * numel, "outputs": outputs,
     }
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: one DIR/<name>.npy (fp32) per array the timed path's last step returned to its caller --
+    `output` and `input_grad` at the same DUMP_SAMPLE flat [N,T,C,H,W] positions (a seeded randperm, ascending),
+    `shift_grad` whole."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in outputs.items()}
 
 
 # how every secondary leg (rk2d, secondary, tshift, pw_*, bn_bwd_dx) is timed -- stated in the JSON so that nobody compares
@@ -836,6 +862,9 @@ def main():
     ap.add_argument("--settle", type=float, default=0.4,
                     help="seconds of untimed continuous load before the warm-up steps (clock / power settle)")
     ap.add_argument("--dry-run", action="store_true", help="no kernels: launcher / rendezvous / timing only (gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline operator's last timed step computed as "
+                         "DIR/<name>.npy (rank 0; nothing in a dry run)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -847,6 +876,7 @@ def main():
     assert env.world_size == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, env.world_size)
     if dry:
         dry_run(env, args)
+        dp.barrier(env)          # as on the GPU path: every rank reaches destroy_process_group() together
         if env.distributed:
             torch.distributed.destroy_process_group()
         return
@@ -865,7 +895,8 @@ def main():
         except Exception as exc:
             cpu_model = {"error": repr(exc)}
 
-    r = op_bench(env, args.steps, args.warmup, settle_s=args.settle)
+    r = op_bench(env, args.steps, args.warmup, settle_s=args.settle, dump=args.dump_outputs is not None)
+    dumped = dump_outputs(r["outputs"], args.dump_outputs) if args.dump_outputs and env.is_main else None
     t_step = r["elapsed_s"] / args.steps
     bytes_step = r["bytes_fwd"] + r["bytes_bwd"]
     value = env.world_size * bytes_step / t_step / 1e9
@@ -994,6 +1025,8 @@ def main():
             "rccl_ranks": torch.distributed.get_world_size() if env.distributed else 1,
             "allreduce_probe": probe,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         emit(json.dumps(out))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

@@ -4,9 +4,7 @@ reference's quirks, plus INTEGRATION.md's claim that the reference's own rubiksn
 
 The oracle stays "parity unpinned by reference execution"; what these tests buy is that the bit-exact GPU claims
 no longer rest on ONE reading of the reference (VERDICT r01, weak #1)."""
-import importlib
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -246,51 +244,35 @@ def test_2d_tiny_shift_closed_form(oracle, tiny):
 
 
 # ------------------------------------------------------------------------- INTEGRATION.md's central claim
-REF = "/root/reference"
+def _rebuild(v):
+    """An argument of tests/golden/binding_calls.json back as a value: tensors as zeros of the recorded shape / dtype."""
+    if isinstance(v, dict):
+        return torch.zeros(v["tensor"], dtype=getattr(torch, v["dtype"]))
+    if isinstance(v, list):
+        return [_rebuild(e) for e in v]
+    return v
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "rubiksnet", "shiftlib")), reason="reference tree not present")
-def test_reference_shiftlib_binds_to_our_extension_module(monkeypatch):
+def test_reference_shiftlib_binds_to_our_extension_module(golden_dir):
     """`sys.modules["rubiksnet_cuda"] = rubiksnet_amd.rubiksnet_cuda` lets the reference's own
-    rubiksnet/shiftlib run unchanged.  Here (no GPU): the reference package imports over our module, its
-    primitives resolve all six binding names with the positional / keyword arguments they use, and calls get as
-    far as the device assertion (reference) or our binding's device check -- never an AttributeError/TypeError."""
+    rubiksnet/shiftlib run unchanged.  tests/golden/binding_calls.json holds every call the reference's layers and
+    primitives made into its extension module (recorded by importing the reference, gen_binding_calls_golden.py):
+    replayed here (no GPU) with CPU tensors of the recorded shapes, each resolves to one of our six binding names and
+    binds the reference's positional / keyword argument lists, getting as far as our binding's device check -- never
+    an AttributeError/TypeError."""
+    import json
+
     from rubiksnet_amd import rubiksnet_cuda as ours
 
-    for name in list(sys.modules):
-        if name == "rubiksnet" or name.startswith("rubiksnet."):
-            monkeypatch.delitem(sys.modules, name)
-    monkeypatch.setitem(sys.modules, "rubiksnet_cuda", ours)
-    monkeypatch.syspath_prepend(REF)
-    ref3d = importlib.import_module("rubiksnet.shiftlib.rubiks3d.primitive")
-    ref2d = importlib.import_module("rubiksnet.shiftlib.rubiks2d.primitive")
-    assert ref3d.rubiksnet_cuda is ours and ref2d.rubiksnet_cuda is ours
-    for name in ("rubiks_shift_3d_forward_float", "rubiks_shift_3d_forward_double", "rubiks_shift_3d_backward_float",
-                 "rubiks_shift_3d_backward_double", "rubiks2d_forward", "rubiks2d_backward"):
-        assert callable(getattr(ours, name))
-
-    x5, s3 = torch.zeros(1, 2, 3, 4, 4), torch.zeros(3, 3)
-    with pytest.raises(AssertionError):                             # reference: assert x.is_cuda (primitive.py:61)
-        ref3d.rubiks_shift_3d_forward(x5, s3, 1, 0)
-    # past the reference's own asserts, straight into the binding with the reference's argument lists
-    # (rubiks3d/primitive.py:78, :127-138; rubiks2d/primitive.py:56-63, :103-114): our device check must answer
-    with pytest.raises(RuntimeError, match="CUDA"):
-        ours.rubiks_shift_3d_forward_float(x5, s3, [1, 1, 1], [0, 0, 0], False, torch.zeros_like(x5))
-    with pytest.raises(RuntimeError, match="CUDA"):
-        ours.rubiks_shift_3d_backward_float(x5, s3, x5, [1, 1, 1], [0, 0, 0], torch.zeros_like(x5),
-                                            torch.zeros_like(s3), True, 1.0, False)
-    x4, s2 = torch.zeros(2, 3, 4, 4), torch.zeros(2, 3)
-    with pytest.raises(RuntimeError, match="CUDA"):
-        ours.rubiks2d_forward(input=x4, shift=s2, strides=[1, 1], paddings=[0, 0], quantize=False,
-                              output=torch.zeros_like(x4))
-    with pytest.raises(RuntimeError, match="CUDA"):
-        ours.rubiks2d_backward(upstream_grad=x4, input=x4, shift=s2, strides=[1, 1], paddings=[0, 0],
-                               normalize_grad=True, enable_shift_grad=True, quantize=False,
-                               input_grad=torch.zeros_like(x4), shift_grad=torch.zeros_like(s2))
-    # the reference's 2-D backward has no is_cuda assert of its own: it reaches our binding through ITS call site
-    with pytest.raises((RuntimeError, AssertionError)):
-        ref2d.rubiks2d_backward(x4, x4, s2, 1, 0)
-    # and its layers construct on top of it
-    ref_layers = importlib.import_module("rubiksnet.shiftlib")
-    layer = ref_layers.RubiksShift3D(6)
-    assert tuple(layer.shift.shape) == (3, 6)
+    with open(os.path.join(golden_dir, "binding_calls.json")) as f:
+        calls = json.load(f)
+    assert {c["fn"] for c in calls} == {
+        "rubiks_shift_3d_forward_float", "rubiks_shift_3d_forward_double", "rubiks_shift_3d_backward_float",
+        "rubiks_shift_3d_backward_double", "rubiks2d_forward", "rubiks2d_backward"}
+    for c in calls:
+        fn = getattr(ours, c["fn"])
+        assert callable(fn)
+        args = [_rebuild(a) for a in c["args"]]
+        kwargs = {k: _rebuild(v) for k, v in c["kwargs"].items()}
+        with pytest.raises(RuntimeError, match="CUDA"):
+            fn(*args, **kwargs)
