@@ -128,6 +128,12 @@ def _presoft_table():
     return getattr(_TABLES, "presoft", None)
 
 
+def _saved_tensor_hooks_active():
+    """True inside torch.autograd.graph.saved_tensors_hooks (what a non-reentrant torch.utils.checkpoint installs)."""
+    top = getattr(torch._C._autograd, "_top_saved_tensors_default_hooks", None)
+    return top is not None and top(False) is not None
+
+
 @contextlib.contextmanager
 def presoftened(module):
     """Inside the block, `AttentionShift.soft_taps()` of every layer of `module` returns its slice of a batched evaluation
@@ -204,9 +210,15 @@ class AttentionShift(nn.Module):
         table = _presoft_table()
         if table is not None:
             hit = table.get(id(self))
-            if hit is not None:
+            # the group's first layer to run WITH grad mode on makes the group's node: one made under no_grad (taps read
+            # for logging, the forward of a reentrant checkpoint) would have no graph, and every later layer of the group
+            # would silently lose its d(weight) -- such a caller takes its own node below.  So does a layer inside a
+            # non-reentrant checkpoint (saved-tensor hooks active): its recompute runs outside the block, and must save
+            # exactly what the forward saved
+            if (hit is not None and (hit[0]["outs"] is not None or torch.is_grad_enabled())
+                    and not _saved_tensor_hooks_active()):
                 group, i = hit
-                if group["outs"] is None:                       # the group's first layer to run makes the group's node
+                if group["outs"] is None:
                     group["outs"] = _SoftTapsManyFunc.apply(group["plan"], *[m.weight for m in group["members"]])
                 return group["outs"][i]
         if w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.shape[1] == 3:

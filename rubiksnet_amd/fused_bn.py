@@ -520,7 +520,7 @@ def bn_relu(bn, x, relu=True):
         rv = bn.running_var if (bn.training and bn.track_running_stats) else None
         return _BNReLUTrain.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, relu, False, _ptr(counter),
                                   take_stats(x) if bn.training else None)
-    if torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad):
+    if torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
         y = bn(x)                                  # frozen-statistics fine-tuning: stock kernels
         return F.relu(y, inplace=True) if relu else y
     return _eval_forward(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)
