@@ -35,9 +35,16 @@
  *     DEVICE, the cached CU count and the "dynamic-LDS ceiling already raised" bit of each kernel instantiation
  *     (rk_common.hpp: raise_dynamic_lds -- hipFuncSetAttribute is per device).  Calls act on the CURRENT device of the
  *     calling thread (hipGetDevice); the Python layer sets it from the tensors' device.
- *   - ONE environment switch, read once per process: RK_SHIFT_KERNELS = auto | column | generic selects which
- *     kernel families the shift operators may use (rk_common.hpp; every family is bit-identical for y and d(x),
- *     tests/test_fallback_paths_gpu.py).  RK_FORCE_GENERIC=1 is the older spelling of `generic`.
+ *   - environment switches, each read once per process:
+ *       RK_SHIFT_KERNELS = auto | column | generic selects which kernel families the shift operators may use
+ *         (rk_common.hpp; every family is bit-identical for y and d(x), tests/test_fallback_paths_gpu.py);
+ *         RK_FORCE_GENERIC=1 is the older spelling of `generic`;
+ *       RK_PW2 = 1 | 0 | 2, RK_PW3 = 1 | 0, RK_PW4 = 1 | 0 | 2: the fp32 1x1 kernel generations (rk_pw.hip: plan_gemm;
+ *         rk_debug_pw_gemm_plan shows the choice);
+ *       RK_SLAB14 = 1 | 0: the slab kernels on 14x14 planes for the backward too / for nothing (unset: forward only;
+ *         rk3d_slab.hip);
+ *       RK_BN_FLAT16 = 0: the 4-element BatchNorm sweep for 16-bit storage too; RK_BN_STATS_FUSED = 0: BatchNorm statistics
+ *         as a statistics kernel + a finisher kernel (rk_bn.hip).
  */
 #ifndef RUBIKS_HIP_H_
 #define RUBIKS_HIP_H_
@@ -75,6 +82,15 @@ unsigned rk_debug_peek_launch_tag(void);
 int rk_debug_set_finalize_spins(int spins);
 int rk3d_debug_finalize_only_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
                                  float t_factor, rk_stream_t stream);
+/* the fp32 1x1 GEMM's kernel choice (rk_pw.hip: plan_gemm) with explicit switches RK_PW2 / RK_PW3 / RK_PW4 and CU count, no
+ * device call: the status rk_pw_gemm_{f32,fused_f32,stats_f32,bnbwd_f32} would return before launching and, in out[5], the
+ * generation (1..4, 0: none), its configuration (1: wm, kc; 2: rb, amode, ct; 3: columns per workgroup, workgroups; 4: row
+ * blocks, k-steps) and the statistics tiles of an epilogue call (= rk_pw_gemm_tiles).  aligned: A and X 16-byte aligned;
+ * epi 0 / 1 (statistics) / 2 (BatchNorm backward); res, pro, ma: residual, prologue (ka), output affine (ma) present.
+ * rk_debug_pw_wgrad_plan: the fp32 d(weight)'s kernel (2: rk_pw2.hip, 1: first generation wide, 0: narrow). */
+int rk_debug_pw_gemm_plan(int F, int K, int M, int P, int a_is_mk, int aligned, int epi, int res, int pro, int ma, int pw2,
+                          int pw3, int pw4, int cus, int* out);
+int rk_debug_pw_wgrad_plan(int F, int K, int M, int P, int pw2);
 
 /* ------------------------------------------------------------------------- 3D
  * Replaces rubiks_shift_3d_forward<T>  (cuda_src/rubiks.cpp:181-253) + functor

@@ -29,6 +29,8 @@ SIGNATURES = {
     "rk_device_count": (_i, []),
     "rk_debug_peek_launch_tag": (ctypes.c_uint, []),
     "rk_debug_set_finalize_spins": (_i, [_i]),
+    "rk_debug_pw_gemm_plan": (_i, [_i] * 14 + [_p]),
+    "rk_debug_pw_wgrad_plan": (_i, [_i] * 5),
     "rk3d_debug_finalize_only_f32": (_i, [_p, _sz, _i, _i, _p, _i, ctypes.c_float, _p]),
     "rk3d_forward_f32": (_i, [_p, _p, _p] + _DIMS3 + [_i, _p]),
     "rk3d_forward_f64": (_i, [_p, _p, _p] + _DIMS3 + [_i, _p]),

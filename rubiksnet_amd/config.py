@@ -18,9 +18,10 @@
                                   (attention_shift.presoftened) / one launch per layer and direction
 
 Everything else that used to be tunable from the environment (tile shapes, channel limits, prefetch depths)
-is a constant next to the code it tunes.  The native library has one switch of its own, RK_SHIFT_KERNELS
-(include/rubiks_hip.h), and RK_PW2 = 1 | 0 | 2 (second-generation fp32 1x1 kernels where they are ahead /
-never / wherever they can run).  Tests flip switches with `config.reload()` after changing os.environ.
+is a constant next to the code it tunes.  The native library reads its own switches once per process
+(listed in include/rubiks_hip.h): RK_SHIFT_KERNELS (shift kernel families), RK_PW2 / RK_PW3 / RK_PW4 (the fp32 1x1
+kernel generations, chosen in rk_pw.hip's plan_gemm), RK_SLAB14, RK_BN_FLAT16 and RK_BN_STATS_FUSED.  Tests flip
+switches with `config.reload()` after changing os.environ.
 """
 import dataclasses
 import os

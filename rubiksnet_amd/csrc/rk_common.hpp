@@ -103,7 +103,7 @@ template <typename A> __device__ __forceinline__ A group_sum(A v, int group, A* 
     return r;
 }
 
-// ---- the library's one switch -------------------------------------------------------
+// ---- the shift kernels' switch (the others: include/rubiks_hip.h) -----------------------
 // RK_SHIFT_KERNELS = auto (default) | column | generic, read once per process:
 //   auto    LDS-DMA streaming kernels (plane-group / column-walk / tile, 2-D twins) where a shape qualifies,
 //           then the column kernels, then the per-plane generic kernels

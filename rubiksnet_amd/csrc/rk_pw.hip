@@ -18,10 +18,7 @@
 #include <type_traits>
 #include "rk_common.hpp"
 #include "rk3d_generic.hpp"
-#include <cstdio>
-#include "rk_pw2.hpp"
-#include "rk_pw3.hpp"
-#include "rk_pw4.hpp"
+#include "rk_pw_plan.hpp"
 
 namespace rk {
 namespace pw {
@@ -63,11 +60,6 @@ struct PwDims {
     int WM, WN;             // waves along M / along N (WM * WN = 4); workgroup tile = 64 WM rows x 128 WN columns
 };
 
-
-// Inference-time fusion of the block's BatchNorms into the GEMM (eval mode: running statistics are constants):
-//   prologue on the streamed operand, per input channel k:   x' = relu?(ka[k] x + kb[k])   (relu(bn1(x)) -> conv2)
-//   epilogue on the result, per output channel m:             y  = relu?(ma[m] y + mb[m])   (relu(bn2(conv2(.))))
-// NULL pointers switch a stage off.
 // eval-mode BatchNorm as a per-channel affine map: a = gamma / sqrt(var + eps), b = beta - mean a (one launch instead of
 // the five elementwise PyTorch kernels per BatchNorm and forward)
 __global__ __launch_bounds__(kBlock) void k_bn_fold(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -92,10 +84,10 @@ __global__ __launch_bounds__(kBlock) void k_bn_fold_many(const FoldJob* __restri
     ab[total + j.off + c] = fmaf(-j.mean[c], s, j.beta[c]);
 }
 
-struct PwFuse {
-    const float* ka; const float* kb; const float* ma; const float* mb;
-    int relu_in, relu_out;
-};
+// Inference-time fusion of the block's BatchNorms into the GEMM (eval mode: running statistics are constants):
+//   prologue on the streamed operand, per input channel k:   x' = relu?(ka[k] x + kb[k])   (relu(bn1(x)) -> conv2)
+//   epilogue on the result, per output channel m:             y  = relu?(ma[m] y + mb[m])   (relu(bn2(conv2(.))))
+// NULL pointers switch a stage off (GFuse, rk_pw_plan.hpp).
 constexpr int kProK = 336;               // input channels a prologue supports (320, padded to whole chunks of 12 / 16)
 
 // Training-mode fusions of the block's BatchNorms into the GEMM epilogue (rubiksnet/backbone.py:
@@ -108,13 +100,7 @@ constexpr int kProK = 336;               // input channels a prologue supports (
 //   EPI = 2 (d(input) of conv2 = gradient of relu(bn1(x))): the result tile is the gradient da of the activation; with x
 //     read at the same positions the ReLU mask and xhat are recomputed, Y receives dz = da * [a x + b > 0] and the tile's
 //     (sum dz, sum dz * xhat) go to bred[m][j]: k_bn_bwd_reduce (one full read of da and x) becomes one read of x here.
-struct PwTrain {
-    float4* stats;                                        // EPI 1: [M][J]
-    float2* bred;                                         // EPI 2: [M][J]
-    const float* bx;                                      // EPI 2: the BatchNorm's input x, [F, M, P]
-    const float4* bpack;                                  // EPI 2: [M] (a, b, mean, invstd) of the BatchNorm
-    int J;
-};
+// (GFuse / GTrain: rk_pw_plan.hpp)
 
 // Sum v[idx] over the 32 lanes that share (lane >> 5), for 32 values at once, in 31 shuffles instead of 32 x 5: at each
 // of the 5 butterfly levels a lane keeps one half of its values and hands the other half to its partner (lane distance
@@ -173,8 +159,8 @@ struct AStage {
 // d(input) written once: no memset).
 template <typename T, int WM, int kKC, bool FUSE, bool STEM = false, int S2 = 0, int EPI = 0>
 __global__ __launch_bounds__(kBlock, ((WM == 2 && kKC == 16 && sizeof(T) == 4) ? 1 : 2)) void k_pw_gemm(const float* __restrict__ A, const T* __restrict__ X,
-                                                    const T* __restrict__ R, T* __restrict__ Y, PwDims d, PwFuse fz,
-                                                    PwTrain tr) {
+                                                    const T* __restrict__ R, T* __restrict__ Y, PwDims d, GFuse fz,
+                                                    GTrain tr) {
     using Raw = typename Px4<T>::Raw;
     constexpr int MT = 64 * WM, WN = 4 / WM;
     __shared__ float As[2][kKC * MT];
@@ -282,7 +268,7 @@ __global__ __launch_bounds__(kBlock, ((WM == 2 && kKC == 16 && sizeof(T) == 4) ?
     }
 
     if constexpr (EPI != 0 && std::is_same<T, float>::value && S2 != 2) {
-        // training epilogues (PwTrain above).  Every lane walks every row: the shuffles need the whole wave.  One 32-row
+        // training epilogues (GTrain).  Every lane walks every row: the shuffles need the whole wave.  One 32-row
         // block at a time (its 16 rows per lane -> 32 partial sums -> folded over the 32 lanes of the half wave), the
         // residual / x rows of 8 rows requested together before the first is used.
         const long long tj = (long long)blockIdx.x * WN + wn;
@@ -1358,151 +1344,228 @@ inline int make_wg(WgDims& d, int F, int K, int M, int P, bool odd = false) {
 }  // namespace pw
 }  // namespace rk
 
+namespace rk {
+namespace pw {
+
+// ---------------------------------------------------------------------------------------------
+// Which generation runs an fp32 GEMM call (rk_pw_plan.hpp).  No HIP call: the CU count is an argument.
+Modes env_modes() {
+    static const Modes m = [] {
+        auto mode = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 1; };
+        return Modes{mode("RK_PW2"), mode("RK_PW3"), mode("RK_PW4")};
+    }();
+    return m;
+}
+
+static long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// rk_pw4.hip: one instance per (K, M) -- 4 row blocks for 49..64 rows / 45..56 input channels, 5 for 65..80 / 61..72.
+// Its policy (RK_PW4 = 1): at least 4 096 column tiles (below, rk_pw2.hip's shorter-lived waves win), and not the 72-channel
+// statistics + residual call (38 records per tile: level with rk_pw2.hip)
+int pw4_rb(const GemmCall& c, const Modes& m, bool any_size) {
+    const int nrb = (c.M + 15) / 16, nst = (c.K + 3) / 4;
+    const int rb = (nrb == 4 && nst >= 12 && nst <= 14) ? 4 : (nrb == 5 && nst >= 16 && nst <= 18) ? 5 : 0;
+    const long long ntot = (long long)c.F * c.P;
+    if (!m.pw4 || !rb || c.P % 4 != 0 || ntot >= (1ll << 31)) return 0;
+    if (!any_size && m.pw4 != 2 && (cdiv(ntot, 64) < 4096 || (rb == 5 && c.epi == 1 && c.res))) return 0;
+    return rb;
+}
+bool pw4_takes(const GemmCall& c) {
+    return !(c.epi == 2 && (c.pro || c.res)) && (long long)c.F * c.K * c.P >= 256;
+}
+// rk_pw2.hip where it is ahead of rk_pw.hip (tools/pw2_probe.py, [256, K -> M, P]: 1.2-1.4x up to 224 rows, level at 288,
+// behind when A needs the LDS image -- K % 4 != 0 with the [M][K] layout)
+static bool pw2_wanted(bool cfg_ok, const pw2::GCfg& g, const GemmCall& c, const Modes& m) {
+    return m.pw2 && c.P % 4 == 0 && cfg_ok && (m.pw2 == 2 || (g.amode != 2 && c.M <= 224));
+}
+// rk_pw3.hip's instances: [M][K] without the BatchNorm-backward epilogue, [K][M] without prologue / statistics
+static bool pw3_takes(const GemmCall& c) {
+    return c.a_is_mk ? c.epi != 2 : (!c.pro && c.epi != 1);
+}
+
+int gemm_tiles(int F, int K, int M, int P, int a_is_mk, int aligned, const Modes& m, int cus) {
+    if (F <= 0 || P <= 0 || K <= 0 || M <= 0) return 0;
+    int cw;
+    if (m.pw3 && aligned) {
+        if (const int nwg = pw3::plan(F, K, M, P, cus, &cw)) return 2 * nwg;      // per workgroup: its two column halves
+    }
+    const GemmCall stats{F, K, M, P, a_is_mk, aligned, 1, 0, 0, 0};
+    pw2::GCfg g;
+    const bool g_ok = pw2::gemm_cfg(g, K, M, a_is_mk, aligned);
+    const bool w64 = pw4_rb(stats, m, false) || pw2_wanted(g_ok, g, stats, m);
+    return (int)cdiv((long long)F * P, w64 ? 64 : 128);
+}
+
+// In order: rk_pw3.hip, rk_pw4.hip, rk_pw2.hip where their policies want the call, then rk_pw.hip.  A call with a training
+// epilogue is held to the records rk_pw_gemm_tiles promised: the first generation whose policy wants it must take it, and
+// 64-column records promised for a call no policy wants go to whichever 64-column kernel has an instance.
+GemmPlan plan_gemm(const GemmCall& c, const Modes& m, int cus) {
+    const GemmPlan unsupported{RK_ERR_UNSUPPORTED, 0, 0, 0, 0, 0}, bad{RK_ERR_BAD_DIMS, 0, 0, 0, 0, 0};
+    if (c.epi && c.ma) return bad;                                   // (the output affine is an inference stage)
+    const long long ntot = (long long)c.F * c.P;
+    const int tiles = c.epi ? gemm_tiles(c.F, c.K, c.M, c.P, c.a_is_mk, c.aligned, m, cus) : 0;
+    int cw;
+    const int nwg = m.pw3 && c.aligned && !c.ma ? pw3::plan(c.F, c.K, c.M, c.P, cus, &cw) : 0;
+    if (nwg) {
+        if (pw3_takes(c)) return {RK_OK, 3, cw, nwg, 0, tiles};
+        if (c.epi) return unsupported;
+    }
+    if (const int rb = pw4_rb(c, m, false); rb && !(c.epi == 2 && c.res)) {
+        if (pw4_takes(c)) return {RK_OK, 4, rb, rb == 4 ? 14 : 18, 0, tiles};
+        if (c.epi) return unsupported;
+    }
+    pw2::GCfg g;
+    const bool g_ok = pw2::gemm_cfg(g, c.K, c.M, c.a_is_mk, c.aligned);
+    const bool g_takes = g_ok && pw2::gemm_instance(g, c.a_is_mk, c.aligned, c.K, c.M, c.epi, c.pro, c.ma);
+    if (pw2_wanted(g_ok, g, c, m)) {
+        if (g_takes) return {RK_OK, 2, g.rb, g.amode, g.ct, tiles};
+        if (c.epi) return unsupported;
+    }
+    if (c.epi && ntot > 64 && tiles == cdiv(ntot, 64)) {             // 64-column records promised
+        if (const int rb = pw4_rb(c, m, true); rb && pw4_takes(c)) return {RK_OK, 4, rb, rb == 4 ? 14 : 18, 0, tiles};
+        if (g_takes) return {RK_OK, 2, g.rb, g.amode, g.ct, tiles};
+        return unsupported;
+    }
+    if (c.pro && (c.K + 15) / 16 * 16 > kProK) return bad;          // prologue table in LDS
+    if (c.epi && tiles != cdiv(ntot, 128)) return bad;
+    // rows per workgroup tile = 64 wm.  Above 128 rows 64-row tiles win although the streamed operand is then re-read once
+    // per tile (L2 / Infinity Cache absorb it; 288 rows: 101 us against 141 / 179 us with 128 / 256-row tiles, which also
+    // pad 288 to 384 / 512).  K chunk of 12 or 16 (2 waves per SIMD; 18 needs too many registers): the one that pads K less
+    const int wm = c.M > 64 && c.M <= 128 ? 2 : 1;
+    const int kc = (c.K + 11) / 12 * 12 <= (c.K + 15) / 16 * 16 ? 12 : 16;
+    return {RK_OK, 1, wm, kc, 0, tiles};
+}
+
+int plan_wgrad(int F, int K, int M, int P, const Modes& m) {
+    if (m.pw2 && P % 4 == 0 && F > 0 && K > 0 && M > 0) return 2;  // LDS-DMA stages, 16 x 16 x 4 MFMA
+    return use_wide(M, K) ? 1 : 0;
+}
+
+}  // namespace pw
+
+namespace pw2 {
+// RB (row blocks per wave) for nrb row blocks: the one that pads least; ties -> the larger
+static int pick_rb(int nrb) {
+    const int cand[3] = {5, 4, 3};
+    int best = 3, waste = 1 << 30;
+    for (int c : cand) {
+        const int w = (nrb + c - 1) / c * c - nrb;
+        if (w < waste) { waste = w; best = c; }
+    }
+    if (nrb % 3 == 0 && nrb >= 9) best = 3;                 // deep layers: many small units balance best
+    return best;
+}
+// AMODE 0: A [M][K] by 16-byte loads (K % 4 == 0, aligned), 1: A [K][M] by dword loads, 2: an LDS image of A (<= 64 KB)
+bool gemm_cfg(GCfg& c, int K, int M, int a_is_mk, int aligned) {
+    const int nrb = (M + 15) / 16;
+    c.rb = pick_rb(nrb);
+    const int nrg = (nrb + c.rb - 1) / c.rb;
+    if (nrg > 16) return false;
+    c.ct = (nrg % 2 == 0) ? 2 : 1;
+    if (!a_is_mk) c.amode = 1;
+    else if (K % 4 == 0 && aligned) c.amode = 0;
+    else {
+        const int ng = (K + 15) / 16;
+        const size_t bytes = (size_t)16 * ng * (16 * nrb + 4) * sizeof(float);
+        if (bytes > 64 * 1024) return false;
+        c.amode = 2;
+    }
+    return true;
+}
+// is there a k_pw2_gemm instance for configuration c and the call's flags?  [K][M] operands (AMODE 1): none with a prologue,
+// output affine or statistics epilogue; AMODE 0: none with the BatchNorm-backward epilogue
+bool gemm_instance(const GCfg& c, int a_is_mk, int aligned, int K, int M, int epi, int pro, int ma) {
+    if (c.rb < 3 || c.rb > 5) return false;
+    if (c.amode == 0) return a_is_mk && K % 4 == 0 && aligned && epi != 2;
+    if (c.amode == 1) return !a_is_mk && (epi == 2 || (!epi && !pro && !ma));
+    const int nrb = (M + 15) / 16;
+    return c.amode == 2 && (size_t)16 * ((K + 15) / 16) * (16 * nrb + 4) * sizeof(float) <= 64 * 1024;
+}
+}  // namespace pw2
+
+namespace pw3 {
+// One workgroup per CU and launch round, 288 rows (17 or 18 blocks), 12 waves.  Column ranges of 193 .. 224 columns, i.e. 7
+// blocks for the first half and up to 7 for the second: anything else would leave the 7-block wave tiles partly empty.
+int plan(int F, int K, int M, int P, int cus, int* cw) {
+    if (P % 4 || K % 16 || M % 4 || M <= 256 || M > 288 || K > 1024) return 0;
+    const long long ntot = (long long)F * P;
+    const long long rounds = (ntot + (long long)cus * 224 - 1) / ((long long)cus * 224);
+    long long w = (ntot + cus * rounds - 1) / (cus * rounds);
+    w = (w + 3) / 4 * 4;
+    if (w <= 192 || w > 224) return 0;
+    *cw = (int)w;
+    return (int)((ntot + w - 1) / w);
+}
+}  // namespace pw3
+}  // namespace rk
+
 using namespace rk;
 using namespace rk::pw;
 
 namespace {
 
-template <typename T>
-int pw_gemm(const float* A, const void* X_, const void* R_, void* Y_, int F, int K, int M, int P, int a_is_mk,
-            rk_stream_t stream_, const PwFuse* fuse = nullptr, const PwTrain* train = nullptr, int epi = 0) {
-    const T* X = (const T*)X_; const T* R = (const T*)R_; T* Y = (T*)Y_;
-    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
-    const uintptr_t am = 4 * sizeof(T) - 1;
-    if (R && ((uintptr_t)R & am)) return RK_ERR_BAD_DIMS;
-    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0 || K % 2 != 0) return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)X & am) || ((uintptr_t)Y & am)) return RK_ERR_BAD_DIMS;
-    if constexpr (std::is_same<T, float>::value) {
-        static const bool trace = getenv("RK_PW_TRACE") != nullptr;      // debugging aid: one line per call
-        if (trace) fprintf(stderr, "pw_gemm F=%d K=%d M=%d P=%d mk=%d epi=%d R=%d pro=%d outaff=%d p3=%d p4=%d p2=%d\n", F, K, M, P, a_is_mk, epi,
-                           R != nullptr, fuse && fuse->ka, fuse && fuse->ma, pw3::tiles(F, K, M, P), (int)pw4::tiles(F, K, M, P, epi, R != nullptr, false),
-                           (int)pw2::gemm_wanted(K, M, P, a_is_mk, A));
-        // second generation (rk_pw2.hip) where it is ahead; its training epilogues use 64-column tiles
-        // (rk_pw_gemm_tiles() tells the caller which count to allocate)
-        // third kernel (rk_pw3.hip): the LDS-tiled GEMM of the 288-row layers, one workgroup per CU
-        if (pw3::tiles(F, K, M, P) > 0 && !(fuse && fuse->ma) && ((uintptr_t)A & 15) == 0) {
-            const pw2::GFuse f3 = fuse ? pw2::GFuse{fuse->ka, fuse->kb, nullptr, nullptr, fuse->relu_in, 0}
-                                       : pw2::GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-            const pw2::GTrain t3 = train ? pw2::GTrain{train->stats, train->bred, train->bx, train->bpack, train->J}
-                                         : pw2::GTrain{nullptr, nullptr, nullptr, nullptr, 0};
-            const int rc = pw3::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &f3, &t3, epi, (hipStream_t)stream_);
-            if (rc != RK_ERR_UNSUPPORTED || epi) return rc;
-        }
-        // streaming kernel of the shallow layers (rk_pw4.hip): operand in registers, records through a per-wave LDS ring;
-        // its tile records are the 64-column ones of rk_pw2.hip
-        if (pw4::tiles(F, K, M, P, epi, R != nullptr, false) > 0 && !(epi && fuse && fuse->ma) && !(epi == 2 && R)) {
-            const pw2::GFuse f4 = fuse ? pw2::GFuse{fuse->ka, fuse->kb, fuse->ma, fuse->mb, fuse->relu_in, fuse->relu_out}
-                                       : pw2::GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-            const pw2::GTrain t4 = train ? pw2::GTrain{train->stats, train->bred, train->bx, train->bpack, train->J}
-                                         : pw2::GTrain{nullptr, nullptr, nullptr, nullptr, 0};
-            const int rc = pw4::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &f4, &t4, epi, (hipStream_t)stream_, false);
-            if (rc != RK_ERR_UNSUPPORTED || epi) return rc;
-        }
-        if (pw2::gemm_wanted(K, M, P, a_is_mk, A)) {
-            const pw2::GFuse f2 = fuse ? pw2::GFuse{fuse->ka, fuse->kb, fuse->ma, fuse->mb, fuse->relu_in, fuse->relu_out}
-                                       : pw2::GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-            const pw2::GTrain t2 = train ? pw2::GTrain{train->stats, train->bred, train->bx, train->bpack, train->J}
-                                         : pw2::GTrain{nullptr, nullptr, nullptr, nullptr, 0};
-            if (epi && (long long)t2.J != ((long long)F * P + pw2::kTileCols - 1) / pw2::kTileCols) return RK_ERR_BAD_DIMS;
-            const int rc = pw2::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &f2, &t2, epi, (hipStream_t)stream_, nullptr);
-            if (rc != RK_ERR_UNSUPPORTED) return rc;
-            if (epi) return rc;                              // (the tile count was promised for this generation)
-        }
-        // A training epilogue whose caller allocated 64-column tile records (what rk_pw_gemm_tiles() promises whenever
-        // rk_pw4.hip takes the shape) but which no second-generation kernel WANTED -- rk_pw4.hip declines some (epilogue,
-        // residual) pairs and rk_pw2.hip was counted on for them; with RK_PW2=0, or a shape rk_pw2.hip serves only in its
-        // slow operand mode, nobody was left and the first-generation kernel below (128-column records) answered
-        // RK_ERR_BAD_DIMS in the middle of a train step (round-4 advisor finding).  The promise is kept: such a call goes to
-        // whichever 64-column kernel CAN take it, wanted or not.
-        const long long fp = (long long)F * P;
-        if (epi && train && fp > 64 && (long long)train->J == (fp + 63) / 64) {
-            const pw2::GFuse f2 = fuse ? pw2::GFuse{fuse->ka, fuse->kb, fuse->ma, fuse->mb, fuse->relu_in, fuse->relu_out}
-                                       : pw2::GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-            const pw2::GTrain t2{train->stats, train->bred, train->bx, train->bpack, train->J};
-            if (!(fuse && fuse->ma) && !(epi == 2 && R)) {
-                const int rc = pw4::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &f2, &t2, epi, (hipStream_t)stream_, true);
-                if (rc != RK_ERR_UNSUPPORTED) return rc;
-            }
-            return pw2::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &f2, &t2, epi, (hipStream_t)stream_, nullptr);
-        }
-    }
+constexpr GFuse kNoFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
+constexpr GTrain kNoTrain{nullptr, nullptr, nullptr, nullptr, 0};
+
+PwDims pw1_dims(int F, int K, int M, int P, int a_is_mk, int wm) {
     PwDims d;
     d.F = F; d.K = K; d.M = M; d.P = P; d.ntot = (long long)F * P; d.a_is_mk = a_is_mk;
     d.Cin = d.Hin = d.Win = d.Wo = 0;
-    // rows per workgroup tile = 64 wm.  Above 128 rows 64-row tiles win although the streamed operand is then
-    // re-read once per tile (L2 / Infinity Cache absorb it; 288 rows: 101 us against 141 / 179 us with 128 / 256-row
-    // tiles, which also pad 288 to 384 / 512)
-    // (bf16, 288 rows, Large-AQ train step: 64-row tiles 45.1 ms, 128-row 47.1, 256-row 57.7: workgroup count and the
-    // per-chunk latency chain, not the re-read of the streamed operand, bound the bf16 kernel)
-    const int wm = M <= 64 ? 1 : (M <= 128 ? 2 : 1);
     d.WM = wm; d.WN = 4 / wm;
-    const int mt = 64 * wm;
-    const dim3 grid((unsigned)((d.ntot + 128 * d.WN - 1) / (128 * d.WN)), (unsigned)((M + mt - 1) / mt)), block(kBlock);
-    hipStream_t stream = (hipStream_t)stream_;
-    // chunk of 12 or 16 (2 waves per SIMD; 18 needs too many registers): the one that pads K less
-    const int kc = ((K + 11) / 12 * 12 <= (K + 15) / 16 * 16) ? 12 : 16;
-    if constexpr (std::is_same<T, __hip_bfloat16>::value) {
-        if (!(fuse && (fuse->ka || fuse->ma))) {                    // bf16 activations: the bf16-MFMA kernel
-#define RK_PW_B(WMV) do { if (a_is_mk) hipLaunchKernelGGL((k_pw_gemm_bf16<WMV, true>), grid, block, 0, stream, A, X, R, Y, d); \
-                          else hipLaunchKernelGGL((k_pw_gemm_bf16<WMV, false>), grid, block, 0, stream, A, X, R, Y, d); } while (0)
-            if (wm == 1) RK_PW_B(1);
-            else if (wm == 2) RK_PW_B(2);
-            else RK_PW_B(4);
-#undef RK_PW_B
-            return launch_status();
-        }
-    }
-    const bool fused = fuse && (fuse->ka || fuse->ma);
-    if (fused && fuse->ka && (K + 15) / 16 * 16 > kProK) return RK_ERR_BAD_DIMS;      // prologue table in LDS
-    PwFuse fz = fused ? *fuse : PwFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    PwTrain tr = train ? *train : PwTrain{nullptr, nullptr, nullptr, nullptr, 0};
-    if constexpr (std::is_same<T, float>::value) {
-        if (epi) {                                           // training epilogues (fp32): statistics of Y / BN-backward sums
-            if (epi == 1 ? !tr.stats : !(tr.bred && tr.bx && tr.bpack)) return RK_ERR_NULL_POINTER;
-            if (fz.ma || (long long)tr.J != (d.ntot + 127) / 128) return RK_ERR_BAD_DIMS;
-            if (epi == 2 && (((uintptr_t)tr.bx & am) || ((uintptr_t)tr.bpack & 15))) return RK_ERR_BAD_DIMS;
-#define RK_PW_EP(WMV, KCV, FU, EP) hipLaunchKernelGGL((k_pw_gemm<float, WMV, KCV, FU, false, 0, EP>), grid, block, 0, stream, A, X, R, Y, d, fz, tr)
-#define RK_PW_EK(WMV, FU, EP) do { if (kc == 12) RK_PW_EP(WMV, 12, FU, EP); else RK_PW_EP(WMV, 16, FU, EP); } while (0)
-#define RK_PW_EW(FU, EP) do { if (wm == 1) RK_PW_EK(1, FU, EP); else RK_PW_EK(2, FU, EP); } while (0)
-            if (epi == 1) { if (fused) RK_PW_EW(true, 1); else RK_PW_EW(false, 1); }
-            else RK_PW_EW(false, 2);
-#undef RK_PW_EW
-#undef RK_PW_EK
-#undef RK_PW_EP
-            return launch_status();
-        }
-    }
-#define RK_PW_GO(WMV, KCV) do { if (fused) hipLaunchKernelGGL((k_pw_gemm<T, WMV, KCV, true>), grid, block, 0, stream, A, X, R, Y, d, fz, tr); \
-                                else hipLaunchKernelGGL((k_pw_gemm<T, WMV, KCV, false>), grid, block, 0, stream, A, X, R, Y, d, fz, tr); } while (0)
-#define RK_PW_KC(WMV) do { if (kc == 12) RK_PW_GO(WMV, 12); else RK_PW_GO(WMV, 16); } while (0)
-    if (wm == 1) RK_PW_KC(1);
-    else if (wm == 2) RK_PW_KC(2);
-    else RK_PW_KC(4);
+    return d;
+}
+dim3 pw1_grid(const PwDims& d) {
+    return dim3((unsigned)((d.ntot + 128 * d.WN - 1) / (128 * d.WN)), (unsigned)((d.M + 64 * d.WM - 1) / (64 * d.WM)));
+}
+
+// first generation, fp32: k_pw_gemm with 64 wm-row tiles and K chunks of kc; FUSE when a prologue or output affine is on
+int pw1_gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk,
+             const GFuse& fz, const GTrain& tr, int epi, int wm, int kc, hipStream_t stream) {
+    const PwDims d = pw1_dims(F, K, M, P, a_is_mk, wm);
+    const dim3 grid = pw1_grid(d), block(kBlock);
+    const bool fused = fz.ka || fz.ma;
+#define RK_PW_GO(WMV, KCV, FU, EP) hipLaunchKernelGGL((k_pw_gemm<float, WMV, KCV, FU, false, 0, EP>), grid, block, 0, stream, A, X, R, Y, d, fz, tr)
+#define RK_PW_KC(WMV, FU, EP) do { if (kc == 12) RK_PW_GO(WMV, 12, FU, EP); else RK_PW_GO(WMV, 16, FU, EP); } while (0)
+#define RK_PW_WM(FU, EP) do { if (wm == 1) RK_PW_KC(1, FU, EP); else RK_PW_KC(2, FU, EP); } while (0)
+    if (epi == 2) RK_PW_WM(false, 2);                                // training epilogues: statistics of Y / BN-backward sums
+    else if (epi == 1) { if (fused) RK_PW_WM(true, 1); else RK_PW_WM(false, 1); }
+    else if (fused) RK_PW_WM(true, 0);
+    else RK_PW_WM(false, 0);
+#undef RK_PW_WM
 #undef RK_PW_KC
 #undef RK_PW_GO
     return launch_status();
 }
 
-template <typename T>
-int pw_wgrad(const void* dY_, const void* X_, float* dW, int F, int K, int M, int P, void* ws, size_t ws_bytes,
-             rk_stream_t stream_, const float* ka = nullptr, const float* kb = nullptr, int relu_in = 0) {
-    const T* dY = (const T*)dY_; const T* X = (const T*)X_;
-    if (!dY || !X || !dW) return RK_ERR_NULL_POINTER;
-    if constexpr (std::is_same<T, float>::value) {
-        if (pw2::wgrad_wanted(P) && F > 0 && K > 0 && M > 0) {         // second generation: LDS-DMA stages, 16 x 16 x 4 MFMA
-            const int rc = pw2::wgrad((const float*)dY_, (const float*)X_, dW, F, K, M, P, ws, ws_bytes, ka, kb, relu_in,
-                                      (hipStream_t)stream_, nullptr);
-            if (rc != RK_ERR_UNSUPPORTED) return rc;
-        }
+int pw_gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk,
+            rk_stream_t stream_, const GFuse& fz = kNoFuse, const GTrain& tr = kNoTrain, int epi = 0) {
+    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
+    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0 || K % 2 != 0) return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)X & 15) || ((uintptr_t)Y & 15) || ((uintptr_t)R & 15)) return RK_ERR_BAD_DIMS;
+    if (epi == 1 ? !tr.stats : epi == 2 && !(tr.bred && tr.bx && tr.bpack)) return RK_ERR_NULL_POINTER;
+    if (epi == 2 && (((uintptr_t)tr.bx & 15) || ((uintptr_t)tr.bpack & 15))) return RK_ERR_BAD_DIMS;
+    const GemmCall c{F, K, M, P, a_is_mk, ((uintptr_t)A & 15) == 0, epi, R != nullptr, fz.ka != nullptr, fz.ma != nullptr};
+    const GemmPlan pl = plan_gemm(c, env_modes(), device_cus());
+    if (pl.rc) return pl.rc;
+    if (epi && tr.J != pl.tiles) return RK_ERR_BAD_DIMS;
+    hipStream_t stream = (hipStream_t)stream_;
+    switch (pl.gen) {
+        case 2: return pw2::gemm(A, X, R, Y, F, K, M, P, a_is_mk, fz, tr, epi, stream, pw2::GCfg{pl.c0, pl.c1, pl.c2});
+        case 3: return pw3::gemm(A, X, R, Y, F, K, M, P, a_is_mk, fz, tr, epi, stream, pl.c0, pl.c1);
+        case 4: return pw4::gemm(A, X, R, Y, F, K, M, P, a_is_mk, fz, tr, epi, stream, pl.c0);
+        default: return pw1_gemm(A, X, R, Y, F, K, M, P, a_is_mk, fz, tr, epi, pl.c0, pl.c1, stream);
     }
+}
+
+// first-generation d(weight): the wide (shared-tile) kernel or the narrow one; bf16 activations: the bf16-MFMA kernel
+template <typename T>
+int pw1_wgrad(const T* dY, const T* X, float* dW, int F, int K, int M, int P, void* ws, size_t ws_bytes, hipStream_t stream,
+              const float* ka, const float* kb, int relu_in, bool wide) {
     WgDims d;
-    // the wide (shared-tile) kernel for > 64 channels; bf16 activations keep the bf16-MFMA kernel
-    const bool wide = use_wide(M, K) && !std::is_same<T, __hip_bfloat16>::value;
     if (int rc = wide ? make_wg_wide(d, F, K, M, P) : make_wg(d, F, K, M, P)) return rc;
     const uintptr_t am = 4 * sizeof(T) - 1;
     if (((uintptr_t)X & am) || ((uintptr_t)dY & am)) return RK_ERR_BAD_DIMS;
     if (!ws || ws_bytes < (size_t)(d.S + kRed) * M * K * sizeof(float)) return RK_ERR_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
     const int nmk = d.MB * d.KB, bpw = nmk < 4 ? nmk : 4, groups = (nmk + bpw - 1) / bpw;
     float* part = (float*)ws;
     float* part2 = part + (size_t)d.S * M * K;
@@ -1510,7 +1573,6 @@ int pw_wgrad(const void* dY_, const void* X_, float* dW, int F, int K, int M, in
     const unsigned gi = (unsigned)((MK + kBlock - 1) / kBlock);
     const bool pro = ka && kb;
     d.ka = ka; d.kb = kb; d.relu_in = relu_in;
-    if (pro && std::is_same<T, __hip_bfloat16>::value) return RK_ERR_BAD_DIMS;      // prologue: fp32 activations only
     if (wide) {
         const int pairs = ((M + 127) / 128) * ((K + 127) / 128);
         if (pro) hipLaunchKernelGGL((k_pw_wgrad_wide<T, true>), dim3((unsigned)(d.S * pairs)), dim3(kBlock), 0, stream, dY, X, part, d);
@@ -1531,27 +1593,60 @@ int pw_wgrad(const void* dY_, const void* X_, float* dW, int F, int K, int M, in
     return launch_status();
 }
 
+int pw_wgrad(const float* dY, const float* X, float* dW, int F, int K, int M, int P, void* ws, size_t ws_bytes,
+             rk_stream_t stream_, const float* ka = nullptr, const float* kb = nullptr, int relu_in = 0) {
+    if (!dY || !X || !dW) return RK_ERR_NULL_POINTER;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int gen = plan_wgrad(F, K, M, P, env_modes());
+    if (gen == 2) return pw2::wgrad(dY, X, dW, F, K, M, P, ws, ws_bytes, ka, kb, relu_in, stream, nullptr);
+    return pw1_wgrad<float>(dY, X, dW, F, K, M, P, ws, ws_bytes, stream, ka, kb, relu_in, gen == 1);
+}
+
 }  // namespace
 
 extern "C" {
 
+// the planned fp32 kernel's partials, and at least the narrow first-generation kernel's: the same workspace serves the
+// bf16 d(weight) (rk_pw_wgrad_bf16), the stem's and the stride-2 shortcut's
 size_t rk_pw_wgrad_workspace_bytes(int F, int K, int M, int P) {
-    WgDims d, w;
-    if (make_wg(d, F, K, M, P) || make_wg_wide(w, F, K, M, P)) return 0;
-    const size_t v1 = (size_t)((d.S > w.S ? d.S : w.S) + kRed) * M * K * sizeof(float);      // whichever kernel is chosen
-    const size_t v2 = pw2::wgrad_workspace_bytes(F, K, M, P);
-    return v1 > v2 ? v1 : v2;
+    WgDims d;
+    if (make_wg(d, F, K, M, P)) return 0;
+    const size_t narrow = (size_t)(d.S + kRed) * M * K * sizeof(float);
+    size_t planned = 0;
+    switch (plan_wgrad(F, K, M, P, env_modes())) {
+        case 2: planned = pw2::wgrad_workspace_bytes(F, K, M, P); break;
+        case 1: if (!make_wg_wide(d, F, K, M, P)) planned = (size_t)(d.S + kRed) * M * K * sizeof(float); break;
+        default: break;
+    }
+    return narrow > planned ? narrow : planned;
 }
 
 // Y[f] = A X[f] (+ R[f]).  a_is_mk != 0: A is [M][K] row-major; else [K][M] (always fp32).  X [F,K,P], Y / R [F,M,P]
 // fp32 or bf16, P % 4 == 0.  R may be NULL (no residual) and may alias Y.
 int rk_pw_gemm_f32(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P,
                    int a_is_mk, rk_stream_t stream) {
-    return pw_gemm<float>(A, X, R, Y, F, K, M, P, a_is_mk, stream);
+    return pw_gemm(A, X, R, Y, F, K, M, P, a_is_mk, stream);
 }
-int rk_pw_gemm_bf16(const float* A, const void* X, const void* R, void* Y, int F, int K, int M, int P, int a_is_mk,
+// bf16 activations: the first generation's bf16-MFMA kernel
+int rk_pw_gemm_bf16(const float* A, const void* X_, const void* R_, void* Y_, int F, int K, int M, int P, int a_is_mk,
                     rk_stream_t stream) {
-    return pw_gemm<__hip_bfloat16>(A, X, R, Y, F, K, M, P, a_is_mk, stream);
+    const __hip_bfloat16* X = (const __hip_bfloat16*)X_; const __hip_bfloat16* R = (const __hip_bfloat16*)R_;
+    __hip_bfloat16* Y = (__hip_bfloat16*)Y_;
+    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
+    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0 || K % 2 != 0) return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)X & 7) || ((uintptr_t)Y & 7) || ((uintptr_t)R & 7)) return RK_ERR_BAD_DIMS;
+    // (Large-AQ train step, 288 rows: 64-row tiles 45.1 ms, 128-row 47.1, 256-row 57.7: workgroup count and the per-chunk
+    // latency chain, not the re-read of the streamed operand, bound the bf16 kernel)
+    const int wm = M > 64 && M <= 128 ? 2 : 1;
+    const PwDims d = pw1_dims(F, K, M, P, a_is_mk, wm);
+    const dim3 grid = pw1_grid(d), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+#define RK_PW_B(WMV) do { if (a_is_mk) hipLaunchKernelGGL((k_pw_gemm_bf16<WMV, true>), grid, block, 0, st, A, X, R, Y, d); \
+                          else hipLaunchKernelGGL((k_pw_gemm_bf16<WMV, false>), grid, block, 0, st, A, X, R, Y, d); } while (0)
+    if (wm == 1) RK_PW_B(1);
+    else RK_PW_B(2);
+#undef RK_PW_B
+    return launch_status();
 }
 // 3x3 / stride 2 / pad 1 convolution, no bias (the stem): W [Cout][Cin][3][3], X [F, Cin, Hin, Win], Y [F, Cout, Ho, Wo],
 // Ho = Hin / 2, Wo = Win / 2 (Hin even, Win % 8 == 0, 9 Cin <= 64).  Same GEMM, im2col gathered on the fly.
@@ -1568,17 +1663,17 @@ static int stem_conv(const float* W, const float* X, float* Y, int F, int Cin, i
     const int mt = 64 * wm;
     const dim3 grid((unsigned)((d.ntot + 128 * d.WN - 1) / (128 * d.WN)), (unsigned)((Cout + mt - 1) / mt)), block(kBlock);
     hipStream_t stream = (hipStream_t)stream_;
-    const PwFuse fz{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const GFuse fz = kNoFuse;
     const float* R = nullptr;
-    if (stats) {                                          // + the statistics of Y for the first block's bn1 (PwTrain)
+    if (stats) {                                          // + the statistics of Y for the first block's bn1 (GTrain)
         if ((long long)J * 128 < d.ntot) return RK_ERR_BAD_DIMS;
-        const PwTrain tr{stats, nullptr, nullptr, nullptr, J};
+        const GTrain tr{stats, nullptr, nullptr, nullptr, J};
         if (wm == 1) hipLaunchKernelGGL((k_pw_gemm<float, 1, 16, false, true, 0, 1>), grid, block, 0, stream, W, X, R, Y, d, fz, tr);
         else if (wm == 2) hipLaunchKernelGGL((k_pw_gemm<float, 2, 12, false, true, 0, 1>), grid, block, 0, stream, W, X, R, Y, d, fz, tr);
         else return RK_ERR_BAD_DIMS;
         return launch_status();
     }
-    const PwTrain tr{nullptr, nullptr, nullptr, nullptr, 0};
+    const GTrain tr = kNoTrain;
     if (wm == 1) hipLaunchKernelGGL((k_pw_gemm<float, 1, 16, false, true>), grid, block, 0, stream, W, X, R, Y, d, fz, tr);
     else if (wm == 2) hipLaunchKernelGGL((k_pw_gemm<float, 2, 12, false, true>), grid, block, 0, stream, W, X, R, Y, d, fz, tr);
     else hipLaunchKernelGGL((k_pw_gemm<float, 4, 16, false, true>), grid, block, 0, stream, W, X, R, Y, d, fz, tr);
@@ -1626,7 +1721,7 @@ int rk_stem_wgrad3x3s2_f32(const float* dY, const float* X, float* dW, int F, in
 // d(input) (mode 2: X = dY [F,K=Cout,Ho,Wo] -> Y = dX [F,M=Cin,Hin,Win], every element written).  Hin, Win even,
 // Wo % 4 == 0, K even.
 static int pw_s2(const float* A, const float* X, float* Y, int F, int K, int M, int Hin, int Win, int mode, int a_is_mk,
-                 rk_stream_t stream_, const PwFuse* fuse = nullptr) {
+                 rk_stream_t stream_, const GFuse* fuse = nullptr) {
     if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
     if (F <= 0 || K <= 0 || M <= 0 || Hin <= 0 || Win <= 0 || Hin % 2 || Win % 2 || K % 2) return RK_ERR_BAD_DIMS;
     if (((Hin / 2) * (Win / 2)) % 4) return RK_ERR_BAD_DIMS;          // output planes of whole 4-pixel groups (Win % 8 == 0: one row each)
@@ -1639,10 +1734,10 @@ static int pw_s2(const float* A, const float* X, float* Y, int F, int K, int M, 
     const int mt = 64 * wm;
     const dim3 grid((unsigned)((d.ntot + 128 * d.WN - 1) / (128 * d.WN)), (unsigned)((M + mt - 1) / mt)), block(kBlock);
     hipStream_t stream = (hipStream_t)stream_;
-    const PwFuse fz = fuse ? *fuse : PwFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const GFuse fz = fuse ? *fuse : kNoFuse;
     if (fuse && fuse->ka && (K + 15) / 16 * 16 > kProK) return RK_ERR_BAD_DIMS;
     const float* R = nullptr;
-    const PwTrain tr{nullptr, nullptr, nullptr, nullptr, 0};
+    const GTrain tr = kNoTrain;
 #define RK_S2_GO(WMV, MODE, FU) hipLaunchKernelGGL((k_pw_gemm<float, WMV, 12, FU, false, MODE>), grid, block, 0, stream, A, X, R, Y, d, fz, tr)
     if (mode == 1 && fuse) { if (wm == 1) RK_S2_GO(1, 1, true); else RK_S2_GO(2, 1, true); }
     else if (mode == 1) { if (wm == 1) RK_S2_GO(1, 1, false); else RK_S2_GO(2, 1, false); }
@@ -1655,7 +1750,7 @@ static int pw_s2(const float* A, const float* X, float* Y, int F, int K, int M, 
 int rk_pw_s2_forward_fused_f32(const float* W, const float* X, float* Y, int F, int Cin, int Cout, int Hin, int Win,
                                const float* ka, const float* kb, int relu_in, rk_stream_t stream) {
     if (!ka || !kb) return RK_ERR_NULL_POINTER;
-    const PwFuse fz{ka, kb, nullptr, nullptr, relu_in, 0};
+    const GFuse fz{ka, kb, nullptr, nullptr, relu_in, 0};
     return pw_s2(W, X, Y, F, Cin, Cout, Hin, Win, 1, 1, stream, &fz);
 }
 int rk_pw_s2_forward_f32(const float* W, const float* X, float* Y, int F, int Cin, int Cout, int Hin, int Win,
@@ -1721,14 +1816,13 @@ int rk_bn_fold_many_f32(const void* jobs, int n, float* ab, long long total, int
                        (const FoldJob*)jobs, ab, total);
     return launch_status();
 }
-// Inference: Y[f] = epi(A pro(X[f])) (+ R[f]) with the per-channel affine (+ReLU) stages of PwFuse above; ka / kb
+// Inference: Y[f] = epi(A pro(X[f])) (+ R[f]) with the per-channel affine (+ReLU) stages of GFuse; ka / kb
 // have K entries, ma / mb have M; a NULL pair switches its stage off.
 int rk_pw_gemm_fused_f32(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P,
                          int a_is_mk, const float* ka, const float* kb, int relu_in, const float* ma,
                          const float* mb, int relu_out, rk_stream_t stream) {
     if ((ka == nullptr) != (kb == nullptr) || (ma == nullptr) != (mb == nullptr)) return RK_ERR_NULL_POINTER;
-    const PwFuse fz{ka, kb, ma, mb, relu_in, relu_out};
-    return pw_gemm<float>(A, X, R, Y, F, K, M, P, a_is_mk, stream, &fz);
+    return pw_gemm(A, X, R, Y, F, K, M, P, a_is_mk, stream, GFuse{ka, kb, ma, mb, relu_in, relu_out});
 }
 // ---- planes with H * W % 4 != 0 (7x7): k_pw_gemm_odd ----
 static int pw_gemm_odd(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk,
@@ -1810,7 +1904,7 @@ int rk_pw_s2_wgrad_odd_f32(const float* dY, const float* X, float* dW, int F, in
     return pw_wgrad_odd(dY, X, dW, F, Cin, Cout, (Hin / 2) * (Win / 2), 1, Hin, Win, ws, ws_bytes, stream);
 }
 
-// ---- training-mode fusions (PwTrain) ----
+// ---- training-mode fusions (GTrain) ----
 // number of 128-column wave tiles of an [F, *, P] tensor = the J of the tile-partial arrays below
 int rk_pw_tiles(int F, int P) {
     if (F <= 0 || P <= 0) return 0;
@@ -1819,51 +1913,52 @@ int rk_pw_tiles(int F, int P) {
 // tile count of the training epilogues of ONE GEMM call (rk_pw_gemm_stats_f32 / rk_pw_gemm_bnbwd_f32 with these
 // arguments): the second-generation kernels (rk_pw2.hip) write one partial per 64 columns, the first per 128.
 int rk_pw_gemm_tiles(const float* A, int F, int K, int M, int P, int a_is_mk) {
-    if (F <= 0 || P <= 0 || K <= 0 || M <= 0) return 0;
-    if (((uintptr_t)A & 15) == 0) {
-        const int t3 = pw3::tiles(F, K, M, P);
-        if (t3 > 0) return t3;
-    }
-    // (the streaming kernel's records are 64-column ones like rk_pw2.hip's; where it takes only some of a shape's epilogues,
-    // rk_pw2.hip takes the others with the same count -- except the [M][K] 54-channel layers, which it takes entirely)
-    const long long t4 = pw4::tiles(F, K, M, P, 1, 0, false);
-    if (t4 > 0) return (int)t4;
-    const int w = pw2::gemm_wanted(K, M, P, a_is_mk, A) ? pw2::kTileCols : 128;
-    return (int)(((long long)F * P + w - 1) / w);
+    return gemm_tiles(F, K, M, P, a_is_mk, ((uintptr_t)A & 15) == 0, env_modes(), device_cus());
 }
+// the planner with explicit switches and CU count (no device call): out = {generation (0: none), its configuration x 3,
+// statistics tiles}; returns the planned call's status
+int rk_debug_pw_gemm_plan(int F, int K, int M, int P, int a_is_mk, int aligned, int epi, int res, int pro, int ma, int pw2,
+                          int pw3, int pw4, int cus, int* out) {
+    const GemmPlan pl = plan_gemm(GemmCall{F, K, M, P, a_is_mk, aligned, epi, res, pro, ma}, Modes{pw2, pw3, pw4}, cus);
+    const int v[5] = {pl.gen, pl.c0, pl.c1, pl.c2, pl.tiles};
+    if (out) for (int i = 0; i < 5; ++i) out[i] = v[i];
+    return pl.rc;
+}
+// d(weight): 2 = rk_pw2.hip, 1 = the first generation's wide kernel, 0 = its narrow one
+int rk_debug_pw_wgrad_plan(int F, int K, int M, int P, int pw2) { return plan_wgrad(F, K, M, P, Modes{pw2, 1, 1}); }
 // forward of a block's conv2 / conv3 in training: Y[f] = A relu?(ka x + kb)(X[f]) (+ R[f]), and the tile statistics of Y
 // (float4 [M][tiles]) for the BatchNorm that consumes Y.  ka / kb NULL: no prologue.
 int rk_pw_gemm_stats_f32(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P,
                          int a_is_mk, const float* ka, const float* kb, int relu_in, void* stats, int tiles,
                          rk_stream_t stream) {
     if ((ka == nullptr) != (kb == nullptr)) return RK_ERR_NULL_POINTER;
-    const PwFuse fz{ka, kb, nullptr, nullptr, relu_in, 0};
-    const PwTrain tr{(float4*)stats, nullptr, nullptr, nullptr, tiles};
-    return pw_gemm<float>(A, X, R, Y, F, K, M, P, a_is_mk, stream, &fz, &tr, 1);
+    return pw_gemm(A, X, R, Y, F, K, M, P, a_is_mk, stream, GFuse{ka, kb, nullptr, nullptr, relu_in, 0},
+                   GTrain{(float4*)stats, nullptr, nullptr, nullptr, tiles}, 1);
 }
 // d(input) of conv2 in training, fused with the first half of bn1's backward: da = A dY (+ R) is masked with
 // [ba x + bb > 0] (x = bn1's input) on its way out -> dZ, and the tile sums (sum dz, sum dz xhat) go to bred (float2
 // [M][tiles]); xhat = (x - mean) invstd.  abmi: [M][4] = (a, b, mean, invstd) per channel, as rk_bn_finish_tiles_f32 packs it.
 int rk_pw_gemm_bnbwd_f32(const float* A, const float* dY, const float* R, float* dZ, int F, int K, int M, int P,
                          int a_is_mk, const float* x, const float* abmi, void* bred, int tiles, rk_stream_t stream) {
-    const PwTrain tr{nullptr, (float2*)bred, x, (const float4*)abmi, tiles};
-    return pw_gemm<float>(A, dY, R, dZ, F, K, M, P, a_is_mk, stream, nullptr, &tr, 2);
+    return pw_gemm(A, dY, R, dZ, F, K, M, P, a_is_mk, stream, kNoFuse, GTrain{nullptr, (float2*)bred, x, (const float4*)abmi, tiles}, 2);
 }
 
 // dW[M][K] (fp32) = sum_f dY[f] X[f]^T.  dY [F,M,P], X [F,K,P] fp32 or bf16, P % 4 == 0.
 int rk_pw_wgrad_f32(const float* dY, const float* X, float* dW, int F, int K, int M, int P, void* ws,
                     size_t ws_bytes, rk_stream_t stream) {
-    return pw_wgrad<float>(dY, X, dW, F, K, M, P, ws, ws_bytes, stream);
+    return pw_wgrad(dY, X, dW, F, K, M, P, ws, ws_bytes, stream);
 }
 // training: d(weight) of conv2 with X = relu?(ka x + kb) recomputed from the block's input (fp32)
 int rk_pw_wgrad_pro_f32(const float* dY, const float* X, float* dW, int F, int K, int M, int P, const float* ka,
                         const float* kb, int relu_in, void* ws, size_t ws_bytes, rk_stream_t stream) {
     if (!ka || !kb) return RK_ERR_NULL_POINTER;
-    return pw_wgrad<float>(dY, X, dW, F, K, M, P, ws, ws_bytes, stream, ka, kb, relu_in);
+    return pw_wgrad(dY, X, dW, F, K, M, P, ws, ws_bytes, stream, ka, kb, relu_in);
 }
 int rk_pw_wgrad_bf16(const void* dY, const void* X, float* dW, int F, int K, int M, int P, void* ws,
                      size_t ws_bytes, rk_stream_t stream) {
-    return pw_wgrad<__hip_bfloat16>(dY, X, dW, F, K, M, P, ws, ws_bytes, stream);
+    if (!dY || !X || !dW) return RK_ERR_NULL_POINTER;
+    return pw1_wgrad((const __hip_bfloat16*)dY, (const __hip_bfloat16*)X, dW, F, K, M, P, ws, ws_bytes, (hipStream_t)stream, nullptr,
+                     nullptr, 0, false);
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@
 #include <type_traits>
 #include "rk_common.hpp"
 #include "rk_dma.hpp"
-#include "rk_pw2.hpp"
+#include "rk_pw_plan.hpp"
 #include "rk_reduce.hpp"
 
 namespace rk {
@@ -562,36 +562,6 @@ __global__ __launch_bounds__(kBlock) void k_pw2_reduce(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// RB (row blocks per wave) for nrb row blocks: the one that pads least; ties -> the larger
-inline int pick_rb(int nrb) {
-    const int cand[3] = {5, 4, 3};
-    int best = 3, waste = 1 << 30;
-    for (int c : cand) {
-        const int w = (nrb + c - 1) / c * c - nrb;
-        if (w < waste) { waste = w; best = c; }
-    }
-    if (nrb % 3 == 0 && nrb >= 9) best = 3;                 // deep layers: many small units balance best
-    return best;
-}
-
-
-inline bool gemm_cfg(GCfg& c, int K, int M, int a_is_mk, const float* A) {
-    const int nrb = (M + 15) / 16;
-    c.rb = pick_rb(nrb);
-    const int nrg = (nrb + c.rb - 1) / c.rb;
-    if (nrg > 16) return false;
-    c.ct = (nrg % 2 == 0) ? 2 : 1;
-    if (!a_is_mk) c.amode = 1;
-    else if (K % 4 == 0 && ((uintptr_t)A & 15) == 0) c.amode = 0;
-    else {
-        const int ng = (K + 15) / 16;
-        const size_t bytes = (size_t)16 * ng * (16 * nrb + 4) * sizeof(float);
-        if (bytes > 64 * 1024) return false;
-        c.amode = 2;
-    }
-    return true;
-}
-
 template <int RB, int AMODE, bool PRO, int EPI, bool OUTAFF>
 int launch_gemm(const float* A, const float* X, const float* R, float* Y, const GDims& d, const GFuse& fz, const GTrain& tr,
                 hipStream_t stream) {
@@ -608,30 +578,25 @@ int launch_gemm(const float* A, const float* X, const float* R, float* Y, const 
     return launch_status();
 }
 
+// the instance for the call's flags (rk_pw.hip's gemm_instance has checked that there is one: [K][M] operands (AMODE 1) have
+// no prologue / output affine / statistics instances, AMODE 0 none for the BatchNorm-backward epilogue)
 template <int RB, int AMODE>
 int launch_gemm_flags(int pro, int epi, int outaff, const float* A, const float* X, const float* R, float* Y, const GDims& d,
                       const GFuse& fz, const GTrain& tr, hipStream_t stream) {
-    if (epi == 2) {
-        if constexpr (AMODE != 0) return launch_gemm<RB, AMODE, false, 2, false>(A, X, R, Y, d, fz, tr, stream);
-        else return RK_ERR_UNSUPPORTED;
+    if constexpr (AMODE == 1) {
+        if (epi == 2) return launch_gemm<RB, 1, false, 2, false>(A, X, R, Y, d, fz, tr, stream);
+        return launch_gemm<RB, 1, false, 0, false>(A, X, R, Y, d, fz, tr, stream);
+    } else {
+        if constexpr (AMODE == 2) {
+            if (epi == 2) return launch_gemm<RB, 2, false, 2, false>(A, X, R, Y, d, fz, tr, stream);
+        }
+        if (epi == 1) return pro ? launch_gemm<RB, AMODE, true, 1, false>(A, X, R, Y, d, fz, tr, stream)
+                                 : launch_gemm<RB, AMODE, false, 1, false>(A, X, R, Y, d, fz, tr, stream);
+        if (outaff) return pro ? launch_gemm<RB, AMODE, true, 0, true>(A, X, R, Y, d, fz, tr, stream)
+                               : launch_gemm<RB, AMODE, false, 0, true>(A, X, R, Y, d, fz, tr, stream);
+        return pro ? launch_gemm<RB, AMODE, true, 0, false>(A, X, R, Y, d, fz, tr, stream)
+                   : launch_gemm<RB, AMODE, false, 0, false>(A, X, R, Y, d, fz, tr, stream);
     }
-    if (epi == 1) {
-        if constexpr (AMODE != 1) {
-            return pro ? launch_gemm<RB, AMODE, true, 1, false>(A, X, R, Y, d, fz, tr, stream)
-                       : launch_gemm<RB, AMODE, false, 1, false>(A, X, R, Y, d, fz, tr, stream);
-        } else return RK_ERR_UNSUPPORTED;
-    }
-    if (outaff) {
-        if constexpr (AMODE != 1) {
-            return pro ? launch_gemm<RB, AMODE, true, 0, true>(A, X, R, Y, d, fz, tr, stream)
-                       : launch_gemm<RB, AMODE, false, 0, true>(A, X, R, Y, d, fz, tr, stream);
-        } else return RK_ERR_UNSUPPORTED;
-    }
-    if (pro) {
-        if constexpr (AMODE != 1) return launch_gemm<RB, AMODE, true, 0, false>(A, X, R, Y, d, fz, tr, stream);
-        else return RK_ERR_UNSUPPORTED;
-    }
-    return launch_gemm<RB, AMODE, false, 0, false>(A, X, R, Y, d, fz, tr, stream);
 }
 
 }  // namespace pw2
@@ -643,61 +608,21 @@ using namespace rk::pw2;
 namespace rk {
 namespace pw2 {
 
-// Should this generation run the call?  Measured against rk_pw.hip (tools/pw2_probe.py, [256, K -> M, P]): ahead by 1.2-1.4x
-// up to 224 rows (54 ... 216 channels), level at 288 rows (where both sit at ~55 % of the f32 MFMA rate: DESIGN 3.5c), and
-// behind when A needs the LDS image (K % 4 != 0 with the [M][K] layout: 54 input channels).
-bool gemm_wanted(int K, int M, int P, int a_is_mk, const float* A) {
-    static const int mode = [] { const char* e = getenv("RK_PW2"); return e ? atoi(e) : 1; }();   // 0: off, 2: wherever it can
-    if (mode == 0 || P % 4 != 0) return false;
-    GCfg c;
-    if (!gemm_cfg(c, K, M, a_is_mk, A)) return false;
-    if (mode == 2) return true;
-    return c.amode != 2 && M <= 224;
-}
-bool wgrad_wanted(int P) {
-    static const int mode = [] { const char* e = getenv("RK_PW2"); return e ? atoi(e) : 1; }();
-    return mode != 0 && P % 4 == 0;
-}
-
-// Y[f] = epi(A pro(X[f])) (+ R[f]) on the second-generation kernel;
-// RK_ERR_UNSUPPORTED when the shape / layout has no instance (the caller then runs rk_pw.hip's kernel).
-// cfg_override: rb / amode / ct > 0 replace the planner's choice.
-int gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk,
-         const GFuse* fuse, const GTrain* train, int epi, hipStream_t stream, const GCfg* cfg_override) {
-    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
-    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0) return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)X & 15) || ((uintptr_t)Y & 15) || (R && ((uintptr_t)R & 15))) return RK_ERR_BAD_DIMS;
-    GCfg c;
-    if (!gemm_cfg(c, K, M, a_is_mk, A)) return RK_ERR_UNSUPPORTED;
-    if (cfg_override) {
-        if (cfg_override->rb > 0) c.rb = cfg_override->rb;
-        if (cfg_override->amode >= 0) c.amode = cfg_override->amode;
-        if (cfg_override->ct > 0) c.ct = cfg_override->ct;
-    }
+// Y[f] = epi(A pro(X[f])) (+ R[f]) on the second-generation kernel in configuration c (rk_pw.hip: plan_gemm)
+int gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk, const GFuse& fz,
+         const GTrain& tr, int epi, hipStream_t stream, const GCfg& c) {
     GDims d;
     d.F = F; d.K = K; d.M = M; d.P = P; d.ntot = (long long)F * P; d.a_is_mk = a_is_mk;
     const int nrb = (M + 15) / 16;
     d.nrg = (nrb + c.rb - 1) / c.rb; d.ct = c.ct; d.ngroups = (K + 15) / 16; d.mpad = 16 * nrb + 4;
-    if (c.amode == 0 && (!a_is_mk || K % 4 != 0 || ((uintptr_t)A & 15))) return RK_ERR_UNSUPPORTED;
-    if (c.amode == 1 && a_is_mk) return RK_ERR_UNSUPPORTED;
-    if (c.amode == 2 && (size_t)16 * d.ngroups * d.mpad * sizeof(float) > 64 * 1024) return RK_ERR_UNSUPPORTED;
-    GFuse fz = fuse ? *fuse : GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    GTrain tr = train ? *train : GTrain{nullptr, nullptr, nullptr, nullptr, 0};
     const int pro = fz.ka != nullptr, outaff = fz.ma != nullptr;
-    if (epi == 1 && !tr.stats) return RK_ERR_NULL_POINTER;
-    if (epi == 2 && !(tr.bred && tr.bx && tr.bpack)) return RK_ERR_NULL_POINTER;
-    if (epi && (long long)tr.J * 64 < d.ntot) return RK_ERR_BAD_DIMS;
-    if (epi && outaff) return RK_ERR_BAD_DIMS;
 #define RK_G2(RBV) do { \
         if (c.amode == 0) return launch_gemm_flags<RBV, 0>(pro, epi, outaff, A, X, R, Y, d, fz, tr, stream); \
         if (c.amode == 1) return launch_gemm_flags<RBV, 1>(pro, epi, outaff, A, X, R, Y, d, fz, tr, stream); \
         return launch_gemm_flags<RBV, 2>(pro, epi, outaff, A, X, R, Y, d, fz, tr, stream); } while (0)
-    switch (c.rb) {
-        case 3: RK_G2(3);
-        case 4: RK_G2(4);
-        case 5: RK_G2(5);
-        default: return RK_ERR_UNSUPPORTED;
-    }
+    if (c.rb == 3) RK_G2(3);
+    if (c.rb == 4) RK_G2(4);
+    RK_G2(5);
 #undef RK_G2
 }
 
@@ -865,9 +790,17 @@ extern "C" {
 // configuration has no instance.
 int rk_pw2_gemm_cfg_f32(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk,
                         const float* ka, const float* kb, int relu_in, int rb, int amode, int ct, rk_stream_t stream) {
-    const GFuse fz{ka, kb, nullptr, nullptr, relu_in, 0};
-    const GCfg c{rb, amode, ct};
-    return pw2::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &fz, nullptr, 0, (hipStream_t)stream, &c);
+    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
+    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0) return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)X & 15) || ((uintptr_t)Y & 15) || ((uintptr_t)R & 15)) return RK_ERR_BAD_DIMS;
+    const int aligned = ((uintptr_t)A & 15) == 0;
+    GCfg c;
+    if (!gemm_cfg(c, K, M, a_is_mk, aligned)) return RK_ERR_UNSUPPORTED;
+    if (rb > 0) c.rb = rb;
+    if (amode >= 0) c.amode = amode;
+    if (ct > 0) c.ct = ct;
+    if (!gemm_instance(c, a_is_mk, aligned, K, M, 0, ka != nullptr, 0)) return RK_ERR_UNSUPPORTED;
+    return pw2::gemm(A, X, R, Y, F, K, M, P, a_is_mk, GFuse{ka, kb, nullptr, nullptr, relu_in, 0}, GTrain{}, 0, (hipStream_t)stream, c);
 }
 size_t rk_pw2_wgrad_workspace_bytes(int F, int K, int M, int P) { return pw2::wgrad_workspace_bytes(F, K, M, P); }
 int rk_pw2_wgrad_cfg_f32(const float* dY, const float* X, float* dW, int F, int K, int M, int P, void* ws, size_t ws_bytes,

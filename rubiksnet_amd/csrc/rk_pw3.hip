@@ -20,15 +20,12 @@
 #include <type_traits>
 #include "rk_common.hpp"
 #include "rk_dma.hpp"
-#include "rk_pw2.hpp"
-#include "rk_pw3.hpp"
+#include "rk_pw_plan.hpp"
 
 namespace rk {
 namespace pw3 {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-using pw2::GFuse;
-using pw2::GTrain;
 
 struct Dims {
     int F, K, M, P;
@@ -321,70 +318,32 @@ __global__ __launch_bounds__(64 * NRG * 2) void k_pw3_gemm(const float* __restri
 }
 
 // ---- host ----
-struct Plan { int Cw, G, split, nwg; };
-
-// The kernel instance: 288 rows (17 or 18 blocks), 12 waves.  Column ranges of 193 .. 224 columns, i.e. 7 blocks for the
-// first half and up to 7 for the second: anything else would leave the 7-block wave tiles partly empty.
-bool plan(Plan& pl, int F, int K, int M, int P) {
-    static const int mode = [] { const char* e = getenv("RK_PW3"); return e ? atoi(e) : 1; }();
-    if (!mode || P % 4 || K % 16 || M % 4 || M <= 256 || M > 288 || K > 1024) return false;
-    const long long ntot = (long long)F * P;
-    const int cus = device_cus();                    // cached per device, thread-safe (rk_common.hpp)
-    const long long rounds = (ntot + (long long)cus * 224 - 1) / ((long long)cus * 224);
-    long long cw = (ntot + cus * rounds - 1) / (cus * rounds);
-    cw = (cw + 3) / 4 * 4;
-    if (cw <= 192 || cw > 224) return false;
-    pl.Cw = (int)cw;
-    pl.split = 112;
-    pl.G = (pl.Cw / 4) | 1;
-    pl.nwg = (int)((ntot + cw - 1) / cw);
-    return true;
-}
-
-int tiles(int F, int K, int M, int P) {
-    Plan pl;
-    return plan(pl, F, K, M, P) ? 2 * pl.nwg : 0;
-}
-
+// the kernel instance: 288 rows (17 or 18 blocks of 16), 12 waves, cw columns per workgroup (rk_pw.hip: pw3::plan)
 template <bool A_MK, bool PRO, int EPI>
-int launch(const float* A, const float* X, const float* R, float* Y, const Dims& d, const Plan& pl, const GFuse& fz,
-           const GTrain& tr, hipStream_t stream) {
+int launch(const float* A, const float* X, const float* R, float* Y, const Dims& d, int nwg, const GFuse& fz, const GTrain& tr,
+           hipStream_t stream) {
     constexpr int RB = 3, NRG = 6, CB = 7;
     const int abytes = 16 * RB * NRG * kKC * 4;
-    const int npx = (kKC * pl.G * 16 + 1023) / 1024;
+    const int npx = (kKC * d.G * 16 + 1023) / 1024;
     const size_t lds = (size_t)kNS * (abytes + npx * 1024) + (PRO ? 2 * d.K * sizeof(float) : 0);
     static DynLdsRaised raised;                      // per instance and device (rk_common.hpp)
     if (const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_pw3_gemm<RB, NRG, CB, A_MK, PRO, EPI>), lds, raised))
         return rc;
-    hipLaunchKernelGGL((k_pw3_gemm<RB, NRG, CB, A_MK, PRO, EPI>), dim3((unsigned)pl.nwg), dim3(64 * NRG * 2), lds, stream, A, X, R,
+    hipLaunchKernelGGL((k_pw3_gemm<RB, NRG, CB, A_MK, PRO, EPI>), dim3((unsigned)nwg), dim3(64 * NRG * 2), lds, stream, A, X, R,
                        Y, d, fz, tr);
     return launch_status();
 }
 
-int gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk, const GFuse* fuse,
-         const GTrain* train, int epi, hipStream_t stream) {
-    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
-    Plan pl;
-    if (!plan(pl, F, K, M, P)) return RK_ERR_UNSUPPORTED;
-    if (((uintptr_t)A & 15) || ((uintptr_t)X & 15)) return RK_ERR_UNSUPPORTED;
-    GFuse fz = fuse ? *fuse : GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    GTrain tr = train ? *train : GTrain{nullptr, nullptr, nullptr, nullptr, 0};
-    if (fz.ma) return RK_ERR_UNSUPPORTED;                   // (inference epilogue: the other generations)
-    const bool pro = fz.ka != nullptr;
-    if (epi == 1 && !tr.stats) return RK_ERR_NULL_POINTER;
-    if (epi == 2 && !(tr.bred && tr.bx && tr.bpack)) return RK_ERR_NULL_POINTER;
-    if (epi && tr.J != 2 * pl.nwg) return RK_ERR_BAD_DIMS;
+int gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk, const GFuse& fz,
+         const GTrain& tr, int epi, hipStream_t stream, int cw, int nwg) {
     Dims d;
-    d.F = F; d.K = K; d.M = M; d.P = P; d.ntot = (long long)F * P; d.Cw = pl.Cw; d.G = pl.G; d.split = pl.split;
+    d.F = F; d.K = K; d.M = M; d.P = P; d.ntot = (long long)F * P; d.Cw = cw; d.G = (cw / 4) | 1; d.split = 112;
     d.nstages = K / kKC; d.a_is_mk = a_is_mk;
-    if (a_is_mk) {
-        if (epi == 1) return pro ? launch<true, true, 1>(A, X, R, Y, d, pl, fz, tr, stream) : launch<true, false, 1>(A, X, R, Y, d, pl, fz, tr, stream);
-        if (epi == 2) return RK_ERR_UNSUPPORTED;
-        return pro ? launch<true, true, 0>(A, X, R, Y, d, pl, fz, tr, stream) : launch<true, false, 0>(A, X, R, Y, d, pl, fz, tr, stream);
-    }
-    if (pro || epi == 1) return RK_ERR_UNSUPPORTED;
-    if (epi == 2) return launch<false, false, 2>(A, X, R, Y, d, pl, fz, tr, stream);
-    return launch<false, false, 0>(A, X, R, Y, d, pl, fz, tr, stream);
+    const bool pro = fz.ka != nullptr;
+    if (!a_is_mk) return epi == 2 ? launch<false, false, 2>(A, X, R, Y, d, nwg, fz, tr, stream)
+                                  : launch<false, false, 0>(A, X, R, Y, d, nwg, fz, tr, stream);
+    if (epi == 1) return pro ? launch<true, true, 1>(A, X, R, Y, d, nwg, fz, tr, stream) : launch<true, false, 1>(A, X, R, Y, d, nwg, fz, tr, stream);
+    return pro ? launch<true, true, 0>(A, X, R, Y, d, nwg, fz, tr, stream) : launch<true, false, 0>(A, X, R, Y, d, nwg, fz, tr, stream);
 }
 
 }  // namespace pw3

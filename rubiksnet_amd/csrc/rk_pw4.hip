@@ -26,7 +26,7 @@
 #include <type_traits>
 #include "rk_common.hpp"
 #include "rk_dma.hpp"
-#include "rk_pw4.hpp"
+#include "rk_pw_plan.hpp"
 
 namespace rk {
 namespace pw4 {
@@ -126,7 +126,7 @@ constexpr int maxrec_of(bool ALDS) { return ALDS ? 17 : 19; }       // 8 x 17 KB
 template <int RB, int NST, bool PRO, int EPI, bool RES, bool ALDS>
 __global__ __launch_bounds__(64 * waves_of(ALDS), ALDS ? 1 : 2) void k_pw4_gemm(const float* __restrict__ A, const float* __restrict__ X,
                                                              const float* __restrict__ R, float* __restrict__ Y, Dims d,
-                                                             pw2::GFuse fz, pw2::GTrain tr) {
+                                                             GFuse fz, GTrain tr) {
     static_assert(!(EPI == 2 && (RES || PRO)), "no such instance");
     constexpr int NE = (EPI == 2 || RES) ? 4 * RB : 0;           // epilogue records per tile
     constexpr int NPAD = pad_of(NST + NE, maxrec_of(ALDS));      // dummy records per tile
@@ -391,49 +391,32 @@ __global__ __launch_bounds__(64 * waves_of(ALDS), ALDS ? 1 : 2) void k_pw4_gemm(
 }
 
 // ---- host ----
-struct Inst { int rb, nst; };
-inline bool pick(Inst& in, int K, int M) {
-    const int nrb = (M + 15) / 16, nst = (K + 3) / 4;
-    if (nrb == 4 && nst >= 12 && nst <= 14) { in = Inst{4, 14}; return true; }
-    if (nrb == 5 && nst >= 16 && nst <= 18) { in = Inst{5, 18}; return true; }
-    return false;
-}
-inline int mode() {
-    static const int m = [] { const char* e = getenv("RK_PW4"); return e ? atoi(e) : 1; }();    // 0: off, 2: any size
-    return m;
-}
-inline int num_cus() { return device_cus(); }        // cached per device, thread-safe (rk_common.hpp)
-constexpr long long kMinTiles = 4096;                // below: rk_pw2.hip (more, shorter-lived waves)
-
 template <int RB, int NST, bool PRO, int EPI, bool RES>
-int launch(const float* A, const float* X, const float* R, float* Y, const Dims& d, const pw2::GFuse& fz, const pw2::GTrain& tr,
+int launch(const float* A, const float* X, const float* R, float* Y, const Dims& d, const GFuse& fz, const GTrain& tr,
            hipStream_t stream) {
     constexpr bool ALDS = RB == 5 && EPI != 0;        // (the 72-channel instance with a training epilogue: see the kernel)
     constexpr int NE = (EPI == 2 || RES) ? 4 * RB : 0;
     constexpr int NREC = best_div(NST + NE + pad_of(NST + NE, maxrec_of(ALDS)), maxrec_of(ALDS));
     constexpr int kWaves = waves_of(ALDS);
-    if ((long long)d.F * d.K * d.P < 256) return RK_ERR_UNSUPPORTED;
     constexpr int wgs_per_cu = ALDS ? 1 : 2;
-    const size_t lds = (size_t)kWaves * NREC * 1024 + 8 * NST * sizeof(float) + 16 * RB * sizeof(float4) +
-                       (ALDS ? (size_t)RB * NST * 256 : 0);
-    if (lds > 160 * 1024) return RK_ERR_UNSUPPORTED;
+    constexpr size_t lds = (size_t)kWaves * NREC * 1024 + 8 * NST * sizeof(float) + 16 * RB * sizeof(float4) +
+                           (ALDS ? (size_t)RB * NST * 256 : 0);
+    static_assert(lds <= 160 * 1024, "LDS of a streaming-GEMM instance");
     static DynLdsRaised raised;                      // per instance and device (rk_common.hpp)
     if (const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_pw4_gemm<RB, NST, PRO, EPI, RES, ALDS>), lds, raised))
         return rc;
-    long long wgs = (long long)num_cus() * wgs_per_cu;
+    long long wgs = (long long)device_cus() * wgs_per_cu;
     const long long need = (d.ntiles + kWaves - 1) / kWaves;
     wgs = wgs < need ? wgs : need;
     hipLaunchKernelGGL((k_pw4_gemm<RB, NST, PRO, EPI, RES, ALDS>), dim3((unsigned)wgs), dim3(64 * kWaves), lds, stream, A, X, R, Y, d,
                        fz, tr);
     return launch_status();
 }
+// the instance for the call's flags (rk_pw.hip: pw4_takes -- no prologue or residual with the BatchNorm-backward epilogue)
 template <int RB, int NST>
 int launch_flags(int pro, int epi, int res, const float* A, const float* X, const float* R, float* Y, const Dims& d,
-                 const pw2::GFuse& fz, const pw2::GTrain& tr, hipStream_t stream) {
-    if (epi == 2) {
-        if (pro || res) return RK_ERR_UNSUPPORTED;
-        return launch<RB, NST, false, 2, false>(A, X, R, Y, d, fz, tr, stream);
-    }
+                 const GFuse& fz, const GTrain& tr, hipStream_t stream) {
+    if (epi == 2) return launch<RB, NST, false, 2, false>(A, X, R, Y, d, fz, tr, stream);
 #define RK_P4(E) do { \
         if (pro) return res ? launch<RB, NST, true, E, true>(A, X, R, Y, d, fz, tr, stream) \
                             : launch<RB, NST, true, E, false>(A, X, R, Y, d, fz, tr, stream); \
@@ -444,42 +427,15 @@ int launch_flags(int pro, int epi, int res, const float* A, const float* X, cons
 #undef RK_P4
 }
 
-// epi / res: the epilogue the call will carry.  The 72-channel instance keeps its operand in registers (90 + 80 registers of
-// operand + accumulators: the 256-VGPR limit of two waves per SIMD) for plain / + R calls and in an LDS table for the
-// training epilogues; statistics + residual (38 records per tile) measured level with rk_pw2.hip (161 / 601 us against
-// 160 / 591 at [256, 72 -> 72, 56 x 56 / 112 x 112]) and stays there.
-long long tiles(int F, int K, int M, int P, int epi, int res, bool force) {
-    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0 || (long long)F * P >= (1ll << 31)) return 0;
-    if (mode() == 0) return 0;
-    Inst in;
-    if (!pick(in, K, M)) return 0;
-    const long long nt = ((long long)F * P + 63) / 64;
-    if (!force && mode() != 2) {
-        if (nt < kMinTiles) return 0;
-        if (in.rb == 5 && epi == 1 && res) return 0;
-    }
-    return nt;
-}
-
-int gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk, const pw2::GFuse* fuse,
-         const pw2::GTrain* train, int epi, hipStream_t stream, bool force) {
-    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
-    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0) return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)X & 15) || ((uintptr_t)Y & 15) || (R && ((uintptr_t)R & 15))) return RK_ERR_BAD_DIMS;
-    Inst in;
-    if (!pick(in, K, M)) return RK_ERR_UNSUPPORTED;
-    if (tiles(F, K, M, P, epi, R != nullptr, force) <= 0) return RK_ERR_UNSUPPORTED;
-    pw2::GFuse fz = fuse ? *fuse : pw2::GFuse{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    pw2::GTrain tr = train ? *train : pw2::GTrain{nullptr, nullptr, nullptr, nullptr, 0};
-    if (fz.ma && (epi != 0 || !fz.mb)) return RK_ERR_UNSUPPORTED;
+// Y[f] = epi(A pro(X[f])) (+ R[f]) on the instance with rb row blocks (rk_pw.hip: pw4_rb).  The 72-channel instance keeps its
+// operand in registers (90 + 80 registers of operand + accumulators: the 256-VGPR limit of two waves per SIMD) for plain /
+// + R calls and in an LDS table for the training epilogues
+int gemm(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk, const GFuse& fz,
+         const GTrain& tr, int epi, hipStream_t stream, int rb) {
     const int pro = fz.ka != nullptr, res = R != nullptr;
     Dims d;
     d.F = F; d.K = K; d.M = M; d.P = P; d.ntot = (long long)F * P; d.ntiles = (d.ntot + 63) / 64; d.a_is_mk = a_is_mk;
-    if (epi == 1 && !tr.stats) return RK_ERR_NULL_POINTER;
-    if (epi == 2 && !(tr.bred && tr.bx && tr.bpack)) return RK_ERR_NULL_POINTER;
-    if (epi == 2 && ((uintptr_t)tr.bx & 15)) return RK_ERR_BAD_DIMS;
-    if (epi && (long long)tr.J != d.ntiles) return RK_ERR_BAD_DIMS;
-    if (in.rb == 4) return launch_flags<4, 14>(pro, epi, res, A, X, R, Y, d, fz, tr, stream);
+    if (rb == 4) return launch_flags<4, 14>(pro, epi, res, A, X, R, Y, d, fz, tr, stream);
     return launch_flags<5, 18>(pro, epi, res, A, X, R, Y, d, fz, tr, stream);
 }
 
@@ -494,8 +450,18 @@ using namespace rk;
 int rk_pw4_gemm_f32(const float* A, const float* X, const float* R, float* Y, int F, int K, int M, int P, int a_is_mk,
                     const float* ka, const float* kb, int relu_in, int epi, void* stats, const float* bx, const float* bpack,
                     void* bred, int tiles, rk_stream_t stream) {
-    const pw2::GFuse fz{ka, kb, nullptr, nullptr, relu_in, 0};
-    const pw2::GTrain tr{(float4*)stats, (float2*)bred, bx, (const float4*)bpack, tiles};
-    return pw4::gemm(A, X, R, Y, F, K, M, P, a_is_mk, &fz, &tr, epi, (hipStream_t)stream, true);
+    if (!A || !X || !Y) return RK_ERR_NULL_POINTER;
+    if (F <= 0 || K <= 0 || M <= 0 || P <= 0 || P % 4 != 0) return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)X & 15) || ((uintptr_t)Y & 15) || ((uintptr_t)R & 15)) return RK_ERR_BAD_DIMS;
+    const pw::GemmCall c{F, K, M, P, a_is_mk, 1, epi, R != nullptr, ka != nullptr, 0};
+    const int rb = pw::pw4_rb(c, pw::env_modes(), true);
+    if (!rb) return RK_ERR_UNSUPPORTED;
+    if (epi == 1 && !stats) return RK_ERR_NULL_POINTER;
+    if (epi == 2 && !(bred && bx && bpack)) return RK_ERR_NULL_POINTER;
+    if (epi == 2 && ((uintptr_t)bx & 15)) return RK_ERR_BAD_DIMS;
+    if (epi && tiles != ((long long)F * P + 63) / 64) return RK_ERR_BAD_DIMS;
+    if (!pw::pw4_takes(c)) return RK_ERR_UNSUPPORTED;
+    return pw4::gemm(A, X, R, Y, F, K, M, P, a_is_mk, GFuse{ka, kb, nullptr, nullptr, relu_in, 0},
+                     GTrain{(float4*)stats, (float2*)bred, bx, (const float4*)bpack, tiles}, epi, (hipStream_t)stream, rb);
 }
 }  // extern "C"
