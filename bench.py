@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- RubiksShift3D fwd+bwd effective GB/s vs the MI355X HBM roofline (BASELINE.json
-`metric`, configs[1]), plus RubiksNet-Tiny train-step clips/s, next to the CPU oracle.
+`metric`, configs[1]); with --full also RubiksNet train-step clips/s, next to the CPU oracle.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one forward + one backward of the operator over one batch of synthetic input,
 x [32, 8, 64, 56, 56] fp32 (layout [N,T,C,H,W]), stride 1, pad 0, normalize_grad on.
@@ -11,11 +11,18 @@ either launched by `python -m torch.distributed.run ... bench.py --gpus N` (RANK
 WORLD_SIZE / MASTER_* in the environment), or -- when WORLD_SIZE is not set -- bench.py re-executes
 itself under torch.distributed.run on 127.0.0.1.  Every rank runs the same per-GPU batch: the path
 shards along clips with no data-path collective (weak scaling); `value` is the whole-job aggregate.
-Rank 0 prints ONE JSON line.  `models` holds the model-level legs of BASELINE.json configs[2..4]
-(per-GPU share of the global batch; DDP all-reduce over RCCL for N > 1).
+Rank 0 prints ONE JSON line.
 
-Without a GPU (`--dry-run`, implied when torch.cuda is unavailable) only the launcher, the rendezvous,
-the barrier / max-over-ranks timing and the all-reduce probe run, on gloo: the product has no CPU path.
+A plain run does only what the headline figure needs: set up, settle, the W warm-up steps, the K timed steps,
+--dump-outputs, the result line.  `--full` adds everything else, as separate runs after the timed steps (the CPU
+columns before them): the per-kernel `roofline` passes of the headline operator, the CPU baselines, the model-level
+legs in `models` (BASELINE.json configs[2..4], per-GPU share of the global batch; DDP all-reduce over RCCL for N > 1),
+the all-reduce probe, the input feeder and the secondary kernel legs.  --models / --model-batch / --model-steps /
+--no-cpu / --no-legs narrow what --full runs.
+
+Without a GPU (`--dry-run`, implied when torch.cuda is unavailable) only the launcher, the rendezvous and the
+barrier / max-over-ranks timing run, on gloo: the product has no CPU path.  `--full` adds the all-reduce probe and
+the model legs' control flow on a stub.
 
 `--dump-outputs DIR` writes what the last of the K timed steps returned -- `output`, `input_grad` (the same seeded
 sample of DUMP_SAMPLE positions of each) and `shift_grad` -- as DIR/<name>.npy in fp32.  The inputs are seeded, so
@@ -45,7 +52,7 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def op_bench(env, steps, warmup, nsets=4, settle_s=0.4, dump=False):
+def op_bench(env, steps, warmup, nsets=4, settle_s=0.4, dump=False, kernel_passes=False):
     dev = env.device
     N, T, C, H, W = SHAPE
     numel = N * T * C * H * W
@@ -83,7 +90,7 @@ def op_bench(env, steps, warmup, nsets=4, settle_s=0.4, dump=False):
         torch.cuda.synchronize()
     for _ in range(warmup):
         step()
-    # The K timed steps run bare.  Per-kernel launch durations come from two more passes of the same K launches
+    # The K timed steps run bare.  Per-kernel launch durations (--full) come from more passes of the same K launches
     # right after the bracket closes -- K forwards, then K backwards (+ finalize), each pass bracketed by ONE pair of
     # HIP events on the launch stream: event records between the kernels of a step cost ~15 us/step of marker
     # packets and idle gaps (tools/launch_gap_probe.py), which also changes the clock regime being measured.
@@ -96,6 +103,9 @@ def op_bench(env, steps, warmup, nsets=4, settle_s=0.4, dump=False):
         idx = torch.randperm(numel, generator=rng)[:DUMP_SAMPLE].sort().values.to(dev)
         outputs = {"output": y.view(-1)[idx].cpu().numpy(), "input_grad": gx.view(-1)[idx].cpu().numpy(),
                    "shift_grad": gshift.cpu().numpy()}
+    res = {"elapsed_s": elapsed, "numel": numel, "bytes_fwd": 8 * numel, "bytes_bwd": 12 * numel, "outputs": outputs}
+    if not kernel_passes:
+        return res
 
     def kernel_pass(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -138,15 +148,11 @@ def op_bench(env, steps, warmup, nsets=4, settle_s=0.4, dump=False):
         rc = L.rk3d_backward_finalize_f32(ws.data_ptr(), C, nparts.value, gshift.data_ptr(), 1, 1.0, stream)
         _native.check(rc, "rk3d_backward_finalize_f32")
 
-    fwd_ms = kernel_pass(fwd_only)
-    bwd_ms = kernel_pass(bwd_only)
-    bwd_kernel_ms = kernel_pass(bwd_kernel_only)
-    finalize_ms = kernel_pass(finalize_only)
-    return {
-        "elapsed_s": elapsed, "numel": numel, "fwd_ms": fwd_ms, "bwd_ms": bwd_ms, "bwd_kernel_ms": bwd_kernel_ms,
-        "finalize_ms": finalize_ms,
-        "bytes_fwd": 8 * numel, "bytes_bwd": 12 * numel, "outputs": outputs,
-    }
+    res["fwd_ms"] = kernel_pass(fwd_only)
+    res["bwd_ms"] = kernel_pass(bwd_only)
+    res["bwd_kernel_ms"] = kernel_pass(bwd_kernel_only)
+    res["finalize_ms"] = kernel_pass(finalize_only)
+    return res
 
 
 def dump_outputs(outputs, out_dir):
@@ -655,6 +661,7 @@ MODEL_LEGS = {
     "large-train": ("large", "rubiks3d", None, "train"),            # configs[3], per-GPU share of 256 / 8
     "large-aq-bf16-train": ("large", "rubiks3d-aq", torch.bfloat16, "train"),   # configs[4]
 }
+DEFAULT_MODELS = ",".join(MODEL_LEGS)   # what --full runs without --models
 
 
 def run_in(env, step, min_s=1.5, max_s=12.0):
@@ -811,20 +818,23 @@ def dry_model_leg(env, steps):
 
 
 def dry_run(env, args):
-    """No GPU: everything of the N-rank path that is not the product kernel."""
-    probe = allreduce_probe(env, mbytes=4, iters=3)
+    """No GPU: everything of the N-rank path that is not the product kernel (with --full: of the --full path)."""
+    probe = allreduce_probe(env, mbytes=4, iters=3) if args.full else None
     dt = dp.timed_region(env, lambda: None, args.steps)
-    stub = dry_model_leg(env, args.steps)
+    stub = dry_model_leg(env, args.steps) if args.full else None
     if env.is_main:
-        emit(json.dumps({
+        out = {
             "metric": "RubiksShift3D fwd+bwd GB/s vs HBM roofline", "value": None, "unit": "GB/s",
             "n_gpus": env.world_size, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "dry_run": True, "backend": env.backend, "rccl_ranks": env.world_size, "allreduce_probe": probe,
-            "empty_timed_region_s": dt, "model_leg_stub": stub,
-            "config": {"workload": "dry run on %s: launcher + rendezvous + barrier/max timing + all-reduce only "
-                                   "(the operator has no CPU path)" % env.backend},
-        }))
+            "dry_run": True, "full": args.full, "backend": env.backend, "rccl_ranks": env.world_size,
+            "empty_timed_region_s": dt,
+            "config": {"workload": "dry run on %s: launcher + rendezvous + barrier/max timing%s only "
+                                   "(the operator has no CPU path)" % (env.backend, " + all-reduce" if args.full else "")},
+        }
+        if args.full:
+            out["allreduce_probe"], out["model_leg_stub"] = probe, stub
+        emit(json.dumps(out))
 
 
 _REAL_STDOUT = None
@@ -847,59 +857,10 @@ def emit(line):
     out.flush()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--models", default="tiny-train,tiny-fwd-b64,small-train,large-train,large-aq-bf16-train",
-                    help="comma list of model legs (%s) or 'none'" % ", ".join(MODEL_LEGS))
-    ap.add_argument("--model-batch", type=int, default=32, help="clips per GPU for the train-step legs")
-    ap.add_argument("--model-steps", type=int, default=6)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary kernel legs (2-D, strided / small planes, "
-                    "temporal, GEMM, BatchNorm): what tools/rocprof_stats.sh traces is then the headline operator alone")
-    ap.add_argument("--settle", type=float, default=0.4,
-                    help="seconds of untimed continuous load before the warm-up steps (clock / power settle)")
-    ap.add_argument("--dry-run", action="store_true", help="no kernels: launcher / rendezvous / timing only (gloo)")
-    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what the headline operator's last timed step computed as "
-                         "DIR/<name>.npy (rank 0; nothing in a dry run)")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(args))
-    claim_stdout()
-
-    dry = args.dry_run or not torch.cuda.is_available()
-    env = dp.init_distributed(prefer_gpu=not dry)
-    assert env.world_size == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, env.world_size)
-    if dry:
-        dry_run(env, args)
-        dp.barrier(env)          # as on the GPU path: every rank reaches destroy_process_group() together
-        if env.distributed:
-            torch.distributed.destroy_process_group()
-        return
-    assert env.device.type == "cuda", "bench.py needs a GPU (no CPU fallback for the product path)"
-
-    # The CPU column first (the host legs run BEFORE the GPU legs of the same process, on rank 0 of a
-    # one-GPU job only -- at N > 1 the other ranks would sit in a barrier while rank 0 computes on the host).
-    cpu = cpu_model = None
-    if env.is_main and env.world_size == 1 and not args.no_cpu:
-        try:
-            cpu = cpu_baseline()
-        except Exception as exc:
-            cpu = {"error": repr(exc)}
-        try:
-            cpu_model = cpu_model_baseline()
-        except Exception as exc:
-            cpu_model = {"error": repr(exc)}
-
-    r = op_bench(env, args.steps, args.warmup, settle_s=args.settle, dump=args.dump_outputs is not None)
-    dumped = dump_outputs(r["outputs"], args.dump_outputs) if args.dump_outputs and env.is_main else None
-    t_step = r["elapsed_s"] / args.steps
+def full_legs(env, args, r, cpu, cpu_model):
+    """--full: everything after the timed steps that the headline figure does not need.  Runs on every rank (a DDP model
+    leg is a collective); returns the extra keys of the result line on rank 0, None elsewhere."""
     bytes_step = r["bytes_fwd"] + r["bytes_bwd"]
-    value = env.world_size * bytes_step / t_step / 1e9
     bwd_gbs = r["bytes_bwd"] / (r["bwd_ms"] * 1e-3) / 1e9
     fwd_gbs = r["bytes_fwd"] / (r["fwd_ms"] * 1e-3) / 1e9
     both_gbs = bytes_step / ((r["fwd_ms"] + r["bwd_ms"]) * 1e-3) / 1e9
@@ -944,45 +905,148 @@ def main():
             bnleg = bn_bench(env)
         except Exception as exc:
             bnleg = {"error": repr(exc)}
+    if not env.is_main:
+        return None
+
+    def frac(d, *keys):
+        for k in keys:
+            d = d.get(k) if isinstance(d, dict) else None
+        return round(d, 4) if isinstance(d, float) else None
+    # every other kernel family against ITS roofline, flat, so that the driver's record keeps them (fraction of the 8 TB/s
+    # HBM peak for the streaming kernels: fwd + bwd bytes / fwd + bwd time; of the f32 MFMA peak for the fp32 GEMMs)
+    others = {
+        "shift3d_stride_1_2_2_112to56": frac(secondary, "stride_1_2_2", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift3d_stride_1_2_2_28to14": frac(secondary, "stride_1_2_2_28to14", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift3d_planes_14x14": frac(secondary, "planes_14x14", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift3d_planes_14x14_288ch": frac(secondary, "planes_14x14_288ch", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift3d_planes_14x14_marginal_fwd": frac(secondary, "planes_14x14_launch_cost_fit", "fwd", "marginal_frac_of_hbm_peak"),
+        "shift3d_planes_14x14_marginal_bwd": frac(secondary, "planes_14x14_launch_cost_fit", "bwd", "marginal_frac_of_hbm_peak"),
+        "shift3d_planes_7x7": frac(secondary, "planes_7x7", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift3d_quantize": frac(secondary, "quantize", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift2d_f32_56x56": frac(rk2d, "f32", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift2d_bf16_56x56": frac(rk2d, "bf16", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "shift2d_bf16_14x14": frac(rk2d, "bf16_14x14", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "tshift3_bf16": frac(tshift, "bf16", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "tshift3_f32": frac(tshift, "f32", "fwd_plus_bwd_frac_of_hbm_peak"),
+        "pw_bf16_fwd_hbm": frac(pw16, "fwd", "frac_of_hbm_peak"),
+        "pw_bf16_fwd_residual_hbm": frac(pw16, "fwd_residual", "frac_of_hbm_peak"),
+        "pw_bf16_wgrad_hbm": frac(pw16, "wgrad", "frac_of_hbm_peak"),
+        "pw_f32_288_fwd_mfma": frac(pw32, "14x14_288ch", "fwd", "frac_of_mfma_peak"),
+        "pw_f32_288_dgrad_mfma": frac(pw32, "14x14_288ch", "dgrad", "frac_of_mfma_peak"),
+        "pw_f32_288_wgrad_mfma": frac(pw32, "14x14_288ch", "wgrad", "frac_of_mfma_peak"),
+        "pw_f32_144_fwd_mfma": frac(pw32, "28x28_144ch", "fwd", "frac_of_mfma_peak"),
+        "bn_bwd_dx_14x14_hbm": frac(bnleg, "14x14_288ch", "dx", "frac_of_hbm_peak"),
+    }
+    for leg, rec in models.items():
+        others["model_%s_frac_of_bound" % leg] = frac(rec, "roofline", "frac")
+    return {
+        "roofline": {
+            "kernel": "rk::dma3d::k3d_dma_backward<2,true,1,1,true,false,false> (two 28-row bands per plane): d(x) + d(shift) + row-sum + K5 in ONE launch "
+                      "(= the rk3d_backward_f32 call; the dominant kernel)",
+            "bound": "hbm",
+            "achieved": bwd_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bwd_gbs / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": traffic_src,
+            "avg_launch_ms": r["bwd_ms"], "algorithmic_bytes": r["bytes_bwd"],
+            "two_phase": {"what": "the same backward through rk3d_backward_partials_f32 + rk3d_backward_finalize_f32 "
+                                  "(unfused kernel, then the separate row-sum + K5 kernel)",
+                          "partials_avg_launch_ms": r["bwd_kernel_ms"], "finalize_avg_launch_ms": r["finalize_ms"]},
+            "kernel_timing": "HIP events on the launch stream: K back-to-back launches of this kernel (rotating "
+                             "buffer sets) between one pair of events, right after the wall-clock bracket; the "
+                             "per-launch period includes the ~2 us dependent-kernel boundary (rocprofv3 duration: profiles/)",
+            "forward": {"achieved": fwd_gbs, "frac": fwd_gbs / HBM_PEAK_GBS, "avg_launch_ms": r["fwd_ms"],
+                        "algorithmic_bytes": r["bytes_fwd"]},
+            "fwd_plus_bwd": {"achieved": both_gbs, "frac": both_gbs / HBM_PEAK_GBS,
+                             "frac_of_copy_ceiling": both_gbs / COPY_CEILING_GBS},
+            "others": others,
+            "others_timing": SECONDARY_TIMING,
+        },
+        "cpu_baseline": cpu,
+        "cpu_baseline_model": cpu_model,          # the same record as models["tiny-train"]["cpu_baseline"]
+        "rk2d": rk2d,
+        "tshift": tshift, "pw_bf16": pw16, "pw_f32": pw32, "bn_bwd_dx": bnleg,
+        "secondary": secondary,
+        "model": models.get("tiny-train"),
+        "models": models,
+        "input_pipeline": feeder,
+        "allreduce_probe": probe,
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the kernel passes of `roofline`, the model legs, the all-reduce "
+                         "probe, the input feeder and the secondary kernel legs, and before them the CPU baselines")
+    ap.add_argument("--models", default=None,
+                    help="(--full) comma list of model legs (%s) or 'none'; default: all" % ", ".join(MODEL_LEGS))
+    ap.add_argument("--model-batch", type=int, default=None, help="(--full) clips per GPU for the train-step legs (32)")
+    ap.add_argument("--model-steps", type=int, default=None, help="(--full) timed steps per model leg (6)")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the cpu_baseline leg")
+    ap.add_argument("--no-legs", action="store_true", help="(--full) skip the secondary kernel legs (2-D, strided / small "
+                    "planes, temporal, GEMM, BatchNorm)")
+    ap.add_argument("--settle", type=float, default=0.4,
+                    help="seconds of untimed continuous load before the warm-up steps (clock / power settle)")
+    ap.add_argument("--dry-run", action="store_true", help="no kernels: launcher / rendezvous / timing only (gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline operator's last timed step computed as "
+                         "DIR/<name>.npy (rank 0; nothing in a dry run)")
+    args = ap.parse_args()
+    narrowing = [name for name, given in (("--models", args.models is not None), ("--model-batch", args.model_batch is not None),
+                                          ("--model-steps", args.model_steps is not None), ("--no-cpu", args.no_cpu),
+                                          ("--no-legs", args.no_legs)) if given]
+    if narrowing and not args.full:
+        ap.error("only with --full: %s" % ", ".join(narrowing))
+    args.models = DEFAULT_MODELS if args.models is None else args.models
+    args.model_batch = 32 if args.model_batch is None else args.model_batch
+    args.model_steps = 6 if args.model_steps is None else args.model_steps
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(self_launch(args))
+    claim_stdout()
+
+    dry = args.dry_run or not torch.cuda.is_available()
+    env = dp.init_distributed(prefer_gpu=not dry)
+    assert env.world_size == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, env.world_size)
+    if dry:
+        dry_run(env, args)
+        dp.barrier(env)          # as on the GPU path: every rank reaches destroy_process_group() together
+        if env.distributed:
+            torch.distributed.destroy_process_group()
+        return
+    assert env.device.type == "cuda", "bench.py needs a GPU (no CPU fallback for the product path)"
+
+    # --full: the CPU column first (the host legs run BEFORE the GPU legs of the same process, on rank 0
+    # of a one-GPU job only -- at N > 1 the other ranks would sit in a barrier while rank 0 computes on the host).
+    cpu = cpu_model = None
+    if args.full and env.is_main and env.world_size == 1 and not args.no_cpu:
+        try:
+            cpu = cpu_baseline()
+        except Exception as exc:
+            cpu = {"error": repr(exc)}
+        try:
+            cpu_model = cpu_model_baseline()
+        except Exception as exc:
+            cpu_model = {"error": repr(exc)}
+
+    r = op_bench(env, args.steps, args.warmup, settle_s=args.settle, dump=args.dump_outputs is not None,
+                 kernel_passes=args.full)
+    dumped = dump_outputs(r["outputs"], args.dump_outputs) if args.dump_outputs and env.is_main else None
+    t_step = r["elapsed_s"] / args.steps
+    bytes_step = r["bytes_fwd"] + r["bytes_bwd"]
+    value = env.world_size * bytes_step / t_step / 1e9
+
+    extra = full_legs(env, args, r, cpu, cpu_model) if args.full else None
     dp.barrier(env)
 
     if env.is_main:
-        def frac(d, *keys):
-            for k in keys:
-                d = d.get(k) if isinstance(d, dict) else None
-            return round(d, 4) if isinstance(d, float) else None
-        # every other kernel family against ITS roofline, flat, so that the driver's record keeps them (fraction of the 8 TB/s
-        # HBM peak for the streaming kernels: fwd + bwd bytes / fwd + bwd time; of the f32 MFMA peak for the fp32 GEMMs)
-        others = {
-            "shift3d_stride_1_2_2_112to56": frac(secondary, "stride_1_2_2", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift3d_stride_1_2_2_28to14": frac(secondary, "stride_1_2_2_28to14", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift3d_planes_14x14": frac(secondary, "planes_14x14", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift3d_planes_14x14_288ch": frac(secondary, "planes_14x14_288ch", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift3d_planes_14x14_marginal_fwd": frac(secondary, "planes_14x14_launch_cost_fit", "fwd", "marginal_frac_of_hbm_peak"),
-            "shift3d_planes_14x14_marginal_bwd": frac(secondary, "planes_14x14_launch_cost_fit", "bwd", "marginal_frac_of_hbm_peak"),
-            "shift3d_planes_7x7": frac(secondary, "planes_7x7", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift3d_quantize": frac(secondary, "quantize", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift2d_f32_56x56": frac(rk2d, "f32", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift2d_bf16_56x56": frac(rk2d, "bf16", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "shift2d_bf16_14x14": frac(rk2d, "bf16_14x14", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "tshift3_bf16": frac(tshift, "bf16", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "tshift3_f32": frac(tshift, "f32", "fwd_plus_bwd_frac_of_hbm_peak"),
-            "pw_bf16_fwd_hbm": frac(pw16, "fwd", "frac_of_hbm_peak"),
-            "pw_bf16_fwd_residual_hbm": frac(pw16, "fwd_residual", "frac_of_hbm_peak"),
-            "pw_bf16_wgrad_hbm": frac(pw16, "wgrad", "frac_of_hbm_peak"),
-            "pw_f32_288_fwd_mfma": frac(pw32, "14x14_288ch", "fwd", "frac_of_mfma_peak"),
-            "pw_f32_288_dgrad_mfma": frac(pw32, "14x14_288ch", "dgrad", "frac_of_mfma_peak"),
-            "pw_f32_288_wgrad_mfma": frac(pw32, "14x14_288ch", "wgrad", "frac_of_mfma_peak"),
-            "pw_f32_144_fwd_mfma": frac(pw32, "28x28_144ch", "fwd", "frac_of_mfma_peak"),
-            "bn_bwd_dx_14x14_hbm": frac(bnleg, "14x14_288ch", "dx", "frac_of_hbm_peak"),
-        }
-        for leg, rec in models.items():
-            others["model_%s_frac_of_bound" % leg] = frac(rec, "roofline", "frac")
         out = {
             "metric": "RubiksShift3D fwd+bwd GB/s vs HBM roofline",
             "value": value, "unit": "GB/s", "n_gpus": env.world_size, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * t_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {
                 "workload": "RubiksShift3D fwd+bwd, x [N=32,T=8,C=64,H=56,W=56] fp32 per GPU "
                             "(layout [N,T,C,H,W]), shift U(-1,1) [3,64], stride 1, pad 0, "
@@ -994,37 +1058,10 @@ def main():
             },
             "clips_per_s": env.world_size * SHAPE[0] / t_step,
             "frac_of_hbm_peak": value / env.world_size / HBM_PEAK_GBS,   # per GPU, from the wall-clock value
-            "roofline": {
-                "kernel": "rk::dma3d::k3d_dma_backward<2,true,1,1,true,false,false> (two 28-row bands per plane): d(x) + d(shift) + row-sum + K5 in ONE launch "
-                          "(= the rk3d_backward_f32 call; the dominant kernel)",
-                "bound": "hbm",
-                "achieved": bwd_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bwd_gbs / HBM_PEAK_GBS,
-                "traffic": traffic, "traffic_source": traffic_src,
-                "avg_launch_ms": r["bwd_ms"], "algorithmic_bytes": r["bytes_bwd"],
-                "two_phase": {"what": "the same backward through rk3d_backward_partials_f32 + rk3d_backward_finalize_f32 "
-                                      "(unfused kernel, then the separate row-sum + K5 kernel)",
-                              "partials_avg_launch_ms": r["bwd_kernel_ms"], "finalize_avg_launch_ms": r["finalize_ms"]},
-                "kernel_timing": "HIP events on the launch stream: K back-to-back launches of this kernel (rotating "
-                                 "buffer sets) between one pair of events, right after the wall-clock bracket; the "
-                                 "per-launch period includes the ~2 us dependent-kernel boundary (rocprofv3 duration: profiles/)",
-                "forward": {"achieved": fwd_gbs, "frac": fwd_gbs / HBM_PEAK_GBS, "avg_launch_ms": r["fwd_ms"],
-                            "algorithmic_bytes": r["bytes_fwd"]},
-                "fwd_plus_bwd": {"achieved": both_gbs, "frac": both_gbs / HBM_PEAK_GBS,
-                                 "frac_of_copy_ceiling": both_gbs / COPY_CEILING_GBS},
-                "others": others,
-                "others_timing": SECONDARY_TIMING,
-            },
-            "cpu_baseline": cpu,
-            "cpu_baseline_model": cpu_model,          # the same record as models["tiny-train"]["cpu_baseline"]
-            "rk2d": rk2d,
-            "tshift": tshift, "pw_bf16": pw16, "pw_f32": pw32, "bn_bwd_dx": bnleg,
-            "secondary": secondary,
-            "model": models.get("tiny-train"),
-            "models": models,
-            "input_pipeline": feeder,
             "rccl_ranks": torch.distributed.get_world_size() if env.distributed else 1,
-            "allreduce_probe": probe,
         }
+        if extra is not None:
+            out.update(extra)
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         emit(json.dumps(out))

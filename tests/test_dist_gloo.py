@@ -119,22 +119,31 @@ def test_ddp_gloo_world2(tmp_path, oracle):
     assert np.allclose(unit.numpy(), 1.0, atol=1e-5)          # each replica's shift grad is unit-norm per channel
 
 
-def test_bench_launches_itself_for_two_ranks_dry_run():
-    """`python bench.py --gpus 2` with no torchrun environment re-executes itself under torch.distributed.run on
-    127.0.0.1 (VERDICT r01 #6); without a GPU it takes the dry-run path (launcher, rendezvous, barrier + max-over-ranks
-    timing, all-reduce probe on gloo) and rank 0 prints ONE JSON line."""
-    import json
+def _bench_dry_run(*args):
+    """bench.py in a fresh process with no torchrun environment and no visible GPU; returns the CompletedProcess."""
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["CUDA_VISIBLE_DEVICES"] = ""           # force the CPU path even on a GPU box
     env["HIP_VISIBLE_DEVICES"] = ""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--dry-run"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(args), cwd=ROOT, env=env,
+                          capture_output=True, text=True, timeout=300)
+
+
+def _one_json_line(r):
+    import json
+
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
-    out = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_launches_itself_for_two_ranks_dry_run():
+    """`python bench.py --gpus 2 --full` with no torchrun environment re-executes itself under torch.distributed.run on
+    127.0.0.1 (VERDICT r01 #6); without a GPU it takes the dry-run path (launcher, rendezvous, barrier + max-over-ranks
+    timing, all-reduce probe on gloo) and rank 0 prints ONE JSON line."""
+    out = _one_json_line(_bench_dry_run("--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full"))
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["dry_run"] is True and out["backend"] == "gloo"
     assert out["allreduce_probe"]["ranks"] == 2 and out["allreduce_probe"]["bus_GBps"] > 0
     assert out["steps"] == 2 and out["scaling"] == "weak" and out["metric"].startswith("RubiksShift3D")
@@ -143,3 +152,23 @@ def test_bench_launches_itself_for_two_ranks_dry_run():
     stub = out["model_leg_stub"]
     assert len(stub["run_in_steps"]) == 2 and stub["run_in_steps"][0] == stub["run_in_steps"][1] >= 12
     assert stub["ms_per_step"] >= stub["slowest_rank_sleep_ms"]
+
+
+def test_plain_bench_dry_run_is_the_timed_region_alone():
+    """Without --full the two-rank dry run does the launcher, the rendezvous and the barrier + max-over-ranks bracket
+    only: no all-reduce probe, no model-leg stub."""
+    out = _one_json_line(_bench_dry_run("--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"))
+    assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["dry_run"] is True and out["full"] is False
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["empty_timed_region_s"] >= 0
+    assert out["metric"].startswith("RubiksShift3D") and out["unit"] == "GB/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["value"] is None and out["ms_per_step"] is None
+    assert "allreduce_probe" not in out and "model_leg_stub" not in out
+
+
+@pytest.mark.parametrize("flag", [["--models", "tiny-train"], ["--model-batch", "8"], ["--model-steps", "2"], ["--no-cpu"],
+                                  ["--no-legs"]])
+def test_bench_options_of_full_need_full(flag):
+    """The options that narrow what --full runs are refused without it (nothing would honour them)."""
+    r = _bench_dry_run("--steps", "2", "--warmup", "1", "--dry-run", *flag)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

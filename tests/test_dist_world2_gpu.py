@@ -100,7 +100,7 @@ def test_two_ranks_on_one_gpu_average_the_per_replica_gradients(tmp_path, varian
 
 def test_the_drivers_two_rank_bench_command_runs_on_one_gpu():
     """The command the driver's SCALE run issues for N = 2 -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node 2
-    --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 --steps K --warmup W` -- end to end on the box's one GPU:
+    --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 --steps K --warmup W`, with --full -- end to end on the box's one GPU:
     RK_DIST_BACKEND=gloo (dp.init_distributed) lets both ranks share the device, everything else is the real job -- the
     operator leg on both ranks, barrier + max-over-ranks timing, the Tiny train-step leg under DDP with its collective run-in,
     the all-reduce probe, rank-0-only legs ahead of the final barrier, ONE JSON line from rank 0."""
@@ -112,7 +112,7 @@ def test_the_drivers_two_rank_bench_command_runs_on_one_gpu():
     env.setdefault("OMP_NUM_THREADS", "8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--models", "tiny-train", "--model-steps", "2", "--no-legs"]
+           "--full", "--models", "tiny-train", "--model-steps", "2", "--no-legs"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

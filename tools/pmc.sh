@@ -1,15 +1,16 @@
 #!/usr/bin/env bash
 # Collect PMC counters for the op in separate passes (rocprofv3 --pmc only; no trace domains).
-# usage: [PROG=tools/prof_2d.py] tools/pmc.sh <outdir-under-gpurun_out> [extra args of the driver]
+# usage: RK_PROFILE_DIR=<output dir> [PROG=tools/prof_2d.py] tools/pmc.sh <subdir> [extra args of the driver]
 # (driver defaults to tools/prof_op.py --iters 6)
 set -u
-out="$GRAFT_REPO_ROOT/gpurun_out/$1"; shift
-mkdir -p "$out"
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
+out="${RK_PROFILE_DIR:?set RK_PROFILE_DIR to the output directory}/$1"; shift
+mkdir -p "$out"; out=$(cd "$out" && pwd)
 cd /tmp && export TMPDIR=/tmp
 pass() {  # name, counters...
   local name=$1; shift
   timeout -s KILL 150 rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -o "$name" -- \
-      python "$GRAFT_REPO_ROOT/$PROG" "${PRE[@]}" "${EXTRA[@]}" > "$out/$name.log" 2>&1
+      python "$root/$PROG" "${PRE[@]}" "${EXTRA[@]}" > "$out/$name.log" 2>&1
   echo "pass $name rc=$?"
 }
 EXTRA=("$@")
