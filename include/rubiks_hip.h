@@ -584,6 +584,26 @@ int rk_clip_u8_to_chw_f32(const unsigned char* hwc, const float* mean3, const fl
 int rk_clip_u8_to_chw_bf16(const unsigned char* hwc, const float* mean3, const float* std3, void* chw, int nclips,
                            int H, int W, int CS, rk_stream_t stream);
 
+/* ---- crop, resize and flip on the device: the head of the reference's transform chain ---------------
+ * GroupMultiScaleCrop + GroupRandomHorizontalFlip (training) and GroupScale + GroupCenterCrop / GroupFullResSample /
+ * GroupOverSample (evaluation) of rubiksnet/transforms.py, followed by the tail above, in one launch.
+ * frames [B, T, Hs, Ws, 3] uint8 RGB as a decoder writes them (any alignment); out [B * V, T, 3, Sh, Sw]; output clip
+ * b * V + v is view v of source clip b.  boxes: device int32 [B * V, 9], one record per OUTPUT clip shared by its T
+ * frames: (x0, y0, cw, ch, rw, rh, ox, oy, flip).  An output frame is: the crop [y0 : y0 + ch, x0 : x0 + cw] of the
+ * source frame, resampled to rw x rh exactly as Pillow's Image.resize((rw, rh), BILINEAR) resamples 8-bit data
+ * (horizontal pass to uint8, then vertical; integer weights (int)(w * 2^22 + 0.5) from fp64 triangle-filter
+ * coefficients of support max(in / out, 1)), of that the window [oy : oy + Sh, ox : ox + Sw], mirrored left-right when
+ * flip != 0, then ((v / 255) - mean3[c]) / std3[c] rounded in fp32 as rk_clip_u8_to_chw does: the f32 result is
+ * bit-identical to the reference's chain, the bf16 one is that rounded once to nearest-even.
+ * cw / rw and ch / rh may be at most 8 (17 taps).  The boxes are device data: the launcher cannot check them, the
+ * kernel clamps every read into `frames`, so a bad box gives a meaningless picture, never an out-of-bounds access
+ * (rubiksnet_amd.augment.check_boxes is the host-side check).  Returns RK_ERR_UNSUPPORTED when Sw needs more LDS
+ * than a workgroup has (Sw above ~920); no workspace, no allocation, no host synchronisation.                      */
+int rk_clip_resample_u8_f32(const unsigned char* frames, const int* boxes, const float* mean3, const float* std3,
+                            float* out, int B, int T, int Hs, int Ws, int V, int Sh, int Sw, rk_stream_t stream);
+int rk_clip_resample_u8_bf16(const unsigned char* frames, const int* boxes, const float* mean3, const float* std3,
+                             void* out, int B, int T, int Hs, int Ws, int V, int Sh, int Sw, rk_stream_t stream);
+
 /* ---- squeeze-and-excitation gate of RubiksNet-Small -- widening row f3 of SURVEY 8(f) --------------
  * SELayer (rubiksnet/backbone.py:56-71): y = x * sigmoid(W2 relu(W1 mean_hw(x))).  x, y, dy, dx [F, C, P];
  * mean / gate / dgate [F, C] f32.  squeeze: mean over P; scale: y = x * gate; scale_backward: dx = dy * gate and

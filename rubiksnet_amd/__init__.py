@@ -6,11 +6,12 @@ RubiksShift3D, RubiksShiftBase + functionals), `AttentionShift`, `RubiksNetBackb
 importing the package does not load it, calling an operator does.
 """
 from . import shiftlib  # noqa: F401
+from . import augment  # noqa: F401
 from .attention_shift import AttentionShift
 from .backbone import RubiksNetBackbone
 from .models import RubiksNet
 from .shiftlib import RubiksShift2D, RubiksShift3D, RubiksShiftBase
 
 __all__ = ["RubiksNet", "RubiksNetBackbone", "AttentionShift", "RubiksShift2D", "RubiksShift3D",
-           "RubiksShiftBase", "shiftlib"]
+           "RubiksShiftBase", "shiftlib", "augment"]
 __version__ = "0.1.0"

@@ -136,6 +136,7 @@ SIGNATURES["rk_se_dgate_f32"] = (_i, [_p, _p, _p, _i, _i, _i, _p])
 SIGNATURES["rk_se_scale_add_f32"] = (_i, [_p, _p, _p, ctypes.c_float, _p, _i, _i, _i, _p])
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
+    SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw
     SIGNATURES["rk_se_squeeze_" + _sfx] = (_i, [_p, _p, _i, _i, _i, _p])
     SIGNATURES["rk_se_scale_" + _sfx] = (_i, [_p, _p, _p, _i, _i, _i, _p])
     SIGNATURES["rk_se_scale_backward_" + _sfx] = (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p])
