@@ -32,9 +32,10 @@
  *   - re-entrant and thread-safe: any thread may call any entry point on any device (autograd worker threads,
  *     nn.DataParallel's one-thread-per-device backward).  The only process-wide mutable state is atomic and
  *     order-independent: the launch-tag counter and poll budget of the in-launch finalizers (rk_dma.hpp), and, PER
- *     DEVICE, the cached CU count and the "dynamic-LDS ceiling already raised" bit of each kernel instantiation
- *     (rk_common.hpp: raise_dynamic_lds -- hipFuncSetAttribute is per device).  Calls act on the CURRENT device of the
- *     calling thread (hipGetDevice); the Python layer sets it from the tensors' device.
+ *     DEVICE, the cached CU count, the "dynamic-LDS ceiling already raised" bit of each kernel instantiation
+ *     (rk_common.hpp: raise_dynamic_lds -- hipFuncSetAttribute is per device) and the pointer to the caller's give-up
+ *     record (rk_fin_status_register below: the library stores the pointer, the memory stays the caller's).  Calls act
+ *     on the CURRENT device of the calling thread (hipGetDevice); the Python layer sets it from the tensors' device.
  *   - environment switches, each read once per process:
  *       RK_SHIFT_KERNELS = auto | column | generic selects which kernel families the shift operators may use
  *         (rk_common.hpp; every family is bit-identical for y and d(x), tests/test_fallback_paths_gpu.py);
@@ -82,6 +83,29 @@ unsigned rk_debug_peek_launch_tag(void);
 int rk_debug_set_finalize_spins(int spins);
 int rk3d_debug_finalize_only_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
                                  float t_factor, rk_stream_t stream);
+/* The give-up record of the in-launch finalizers.  Every streaming backward (and the fused BatchNorm statistics) finishes its
+ * per-channel sums inside the producing launch; a finalizer wave that has not seen its partials after the poll budget
+ * (~2 s) gives up and its outputs (gshift / gtaps / dgamma / dbeta / k12 / the BatchNorm statistics) are NaN -- long after
+ * the entry point returned RK_OK.  A registered record makes that give-up distinguishable from NaN data:
+ *   record[0] give-ups (finalizer waves that timed out) since the record was last zeroed
+ *   record[1] launch tag of the first of them (0: none)      record[2] launch tag of the most recent one
+ *   record[3] reserved, 0
+ * (unsigned words; the tag of a launch is what rk_debug_peek_launch_tag returned before it.)  Only a finalizer that gives
+ * up writes, with device-scope atomics; the NaN outputs stay as they are.
+ * rk_fin_status_register acts on the calling thread's current device: `record` is caller-owned device memory of
+ * RK_FIN_STATUS_BYTES, 16-byte aligned and zeroed by the caller, which launches made from then on (any thread, that
+ * device) report into; NULL unregisters.  Returns RK_OK, RK_ERR_NO_DEVICE (no current device, or a device index beyond
+ * the 64 the library keeps per-device state for) or RK_ERR_BAD_DIMS (misaligned).  No allocation, no copy, no
+ * synchronisation, no device call beyond hipGetDevice; the caller reads and re-zeroes the record when it likes (a plain
+ * 16-byte copy on a stream).  A caller that never registers gets the behaviour without a record, bit for bit.  The pointer
+ * travels as a kernel argument, so a captured hipGraph keeps the one it was captured with: a record must outlive every
+ * graph captured while it was registered.
+ * rk3d_debug_finalize_only_status_f32 is rk3d_debug_finalize_only_f32 with an explicit record (NULL allowed) in place of
+ * the registered one; rk3d_debug_finalize_only_f32 itself never reports (record = NULL). */
+#define RK_FIN_STATUS_BYTES 16
+int rk_fin_status_register(void* record);
+int rk3d_debug_finalize_only_status_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
+                                        float t_factor, void* record, rk_stream_t stream);
 /* the fp32 1x1 GEMM's kernel choice (rk_pw.hip: plan_gemm) with explicit switches RK_PW2 / RK_PW3 / RK_PW4 and CU count, no
  * device call: the status rk_pw_gemm_{f32,fused_f32,stats_f32,bnbwd_f32} would return before launching and, in out[5], the
  * generation (1..4, 0: none), its configuration (1: wm, kc; 2: rb, amode, ct; 3: columns per workgroup, workgroups; 4: row

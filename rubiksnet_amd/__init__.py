@@ -3,15 +3,17 @@
 Public surface mirrors the reference package `rubiksnet`: `shiftlib` (RubiksShift2D,
 RubiksShift3D, RubiksShiftBase + functionals), `AttentionShift`, `RubiksNetBackbone`,
 `RubiksNet`.  All device work goes through librubiks_hip.so (include/rubiks_hip.h);
-importing the package does not load it, calling an operator does.
+importing the package does not load it, calling an operator does.  `fin_status` reports an in-launch
+reduction that gave up (its outputs are NaN) as a RubiksHipError.
 """
 from . import shiftlib  # noqa: F401
 from . import augment  # noqa: F401
+from . import fin_status  # noqa: F401
 from .attention_shift import AttentionShift
 from .backbone import RubiksNetBackbone
 from .models import RubiksNet
 from .shiftlib import RubiksShift2D, RubiksShift3D, RubiksShiftBase
 
 __all__ = ["RubiksNet", "RubiksNetBackbone", "AttentionShift", "RubiksShift2D", "RubiksShift3D",
-           "RubiksShiftBase", "shiftlib", "augment"]
+           "RubiksShiftBase", "shiftlib", "augment", "fin_status"]
 __version__ = "0.1.0"

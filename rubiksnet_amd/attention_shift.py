@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _native, config
+from . import _native, config, fin_status
 
 __all__ = ["AttentionShift", "temporal_shift3", "presoftened"]
 
@@ -57,6 +57,7 @@ class _TemporalShift3Func(torch.autograd.Function):
         gx = torch.empty_like(x)
         gtaps = torch.empty_like(taps32)
         L = _native.lib()
+        fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         ws_bytes = int(L.rk_tshift3_backward_workspace_bytes(nt, ctx.n_segment, c, h * w))
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
         _run("rk_tshift3_backward_" + ctx.sfx, x.device, gy.data_ptr(), x.data_ptr(), taps32.data_ptr(),

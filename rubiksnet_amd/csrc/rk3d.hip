@@ -287,21 +287,28 @@ int rk3d_backward_finalize_f32(const void* ws, int C, int partials, float* gshif
 
 // Test hook: ONLY the finalizer waves of a fused 3-D backward (rk3d_dma.hpp, finalizer_wave<3>) on a workspace no producer
 // will ever publish to -- the give-up path: every channel must come back NaN once the poll budget
-// (rk_debug_set_finalize_spins) is spent, and the launch must end.  No product code calls it.
-int rk3d_debug_finalize_only_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
-                                 float t_factor, rk_stream_t stream) {
+// (rk_debug_set_finalize_spins) is spent, and the launch must end.  No product code calls it.  The give-up record is the
+// one given (NULL: none), never the registered one: a deliberate give-up must not dirty the record product launches use.
+int rk3d_debug_finalize_only_status_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
+                                        float t_factor, void* record, rk_stream_t stream) {
     if (!ws || !gshift) return RK_ERR_NULL_POINTER;
     if (C <= 0 || partials <= 0) return RK_ERR_BAD_DIMS;
+    if ((uintptr_t)record & (RK_FIN_STATUS_BYTES - 1)) return RK_ERR_BAD_DIMS;
     if (ws_bytes < (size_t)C * 3 * partials * 16) return RK_ERR_WORKSPACE;
     dma3d::Fin3 fin{};
     fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
     dma::fin_arm(fin.f);
+    fin.f.status = static_cast<unsigned*>(record);
     fin.f.producers = 0;
     fin.gshift = gshift;
     fin.normalize = normalize_grad;
     fin.t_factor = t_factor;
     hipLaunchKernelGGL(k3d_debug_finalize_only, dim3((unsigned)C), dim3(kWave), 0, (hipStream_t)stream, fin, C, partials);
     return launch_status();
+}
+int rk3d_debug_finalize_only_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
+                                 float t_factor, rk_stream_t stream) {
+    return rk3d_debug_finalize_only_status_f32(ws, ws_bytes, C, partials, gshift, normalize_grad, t_factor, nullptr, stream);
 }
 
 }  // extern "C"

@@ -239,9 +239,11 @@ struct Fin {
     unsigned tag;                 // != 0, unique per launch
     int producers;                // producer blocks; blocks beyond are finalizers
     int spins;                    // polls of one lane before its finalizer gives up (~0.25 us each)
+    unsigned* status;             // give-up record of this device (4 words, below), or nullptr: nobody is told
 };
-// The library's only process-wide mutable state, both std::atomic (any thread, any device): the launch-tag counter and
-// the finalizers' poll budget (a test hook: rk_debug_set_finalize_spins, rk_misc.hip).
+// The library's only process-wide mutable state, all std::atomic (any thread, any device): the launch-tag counter, the
+// finalizers' poll budget (a test hook: rk_debug_set_finalize_spins, rk_misc.hip) and, per device, the registered
+// give-up record (rk_fin_status_register, rk_misc.hip).
 inline std::atomic<unsigned>& launch_tag_counter() {
     static std::atomic<unsigned> tag{(unsigned)std::chrono::steady_clock::now().time_since_epoch().count() | 1u};
     return tag;
@@ -256,10 +258,25 @@ inline unsigned next_launch_tag() {
     unsigned t = tag.fetch_add(1, std::memory_order_relaxed);
     return t ? t : tag.fetch_add(1, std::memory_order_relaxed);
 }
-// every launch that hands partials to in-launch finalizers arms its Fin here: a fresh tag + the current poll budget
+// The give-up record: a finalizer that writes NaN also says so in 16 bytes of caller-owned device memory, so that the
+// host can tell "a launch gave up" from "the data was NaN" and name the launch:
+//   [0] fin_collect calls that timed out since the record was last zeroed   [1] launch tag of the first of them (0: none)
+//   [2] launch tag of the most recent one                                   [3] reserved, 0
+// One pointer per device, registered by the caller (NULL = none, the default); a launch reads its device's entry when it
+// is armed and carries it as a kernel argument -- a captured graph keeps the pointer it was captured with.  Only a
+// finalizer that gave up touches the record; producers and the ready path never do.
+inline std::atomic<unsigned*>* fin_status_slot(int dev) {
+    static std::atomic<unsigned*> slots[kMaxDevices];
+    return dev >= 0 && dev < kMaxDevices ? &slots[dev] : nullptr;
+}
+// every launch that hands partials to in-launch finalizers arms its Fin here: a fresh tag, the current poll budget and
+// the current device's give-up record
 inline void fin_arm(Fin& f) {
     f.tag = next_launch_tag();
     f.spins = fin_spin_budget().load(std::memory_order_relaxed);
+    int dev = 0;
+    std::atomic<unsigned*>* slot = hipGetDevice(&dev) == hipSuccess ? fin_status_slot(dev) : nullptr;
+    f.status = slot ? slot->load(std::memory_order_relaxed) : nullptr;
 }
 // A partial is handed over as a PAIR of 8-byte granules at gran[2*at], gran[2*at + 1]:
 //   value granule {fp32 value, tag}   and   check granule {~value bits, tag2},  tag2 = a second word derived from tag.
@@ -346,6 +363,14 @@ __device__ __forceinline__ void fin_load(const Fin& fin, unsigned long long* g, 
         w[k] = __hip_atomic_load(g + at + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// the give-up report of fin_collect as a function of its own (why: at its call site); any lane may call, lane 0 writes
+__device__ __attribute__((noinline, cold)) void fin_report(unsigned* status, unsigned tag) {
+    if (status == nullptr || threadIdx.x != 0) return;
+    __hip_atomic_fetch_add(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned none = 0u;
+    __hip_atomic_compare_exchange_strong(status + 1, &none, tag, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(status + 2, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 // `count` <= P: the partials that exist for this channel (rows keep the stride P)
 template <int D>
 __device__ __forceinline__ bool fin_collect(const Fin& fin, int c, int P, double (&s)[D], int count = -1) {
@@ -390,7 +415,25 @@ __device__ __forceinline__ bool fin_collect(const Fin& fin, int c, int P, double
     }
 #pragma unroll
     for (int k = 0; k < D; ++k) s[k] = wave_sum(s[k]);
-    return __all(ok) != 0;
+    const bool all_ok = __all(ok) != 0;
+    // Gave up (cold; the caller writes NaN): one lane says so in the device's record, layout at fin_status_slot above.
+    // Nothing here runs on the ready path, but the code is part of kernels whose producer loops sit exactly on a
+    // register step, and register allocation is global: written inline, k_tshift3_backward<float, 4, BN> (168 VGPRs, capped)
+    // gained 12 bytes of scratch; as a call, k2d_raw16_backward<bf16, float, 4, BN> went 168 -> 169 VGPRs (3 -> 2 waves per
+    // SIMD).  So the four-sum finalizers (the 2-D BatchNorm-fused backwards) carry it inline and the others call
+    // fin_report; tools/kernel_regs.py compares two builds, profiles/fin_status_regs.txt is the table for this split.
+    if constexpr (D == 4) {
+        if (__ballot(!ok) != 0ull && fin.status != nullptr && lane == 0) {
+            __hip_atomic_fetch_add(fin.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned none = 0u;
+            __hip_atomic_compare_exchange_strong(fin.status + 1, &none, fin.tag, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(fin.status + 2, fin.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else {
+        if (!all_ok && fin.status != nullptr) fin_report(fin.status, fin.tag);
+    }
+    return all_ok;
 }
 
 // ---------------------------------------------------------------------------------------------

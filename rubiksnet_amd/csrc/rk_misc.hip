@@ -107,4 +107,17 @@ int rk_debug_set_finalize_spins(int spins) {
     return rk::dma::fin_spin_budget().exchange(spins > 0 ? spins : rk::dma::kFinSpins, std::memory_order_relaxed);
 }
 
+// The give-up record of the calling thread's current device (rk_dma.hpp: fin_status_slot): 16 bytes of caller-owned, zeroed
+// device memory that in-launch finalizers armed from now on report a give-up into; NULL unregisters.  One atomic store: no
+// allocation, no copy, no synchronisation, no device call beyond hipGetDevice.
+int rk_fin_status_register(void* record) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return RK_ERR_NO_DEVICE;
+    std::atomic<unsigned*>* slot = rk::dma::fin_status_slot(dev);
+    if (!slot) return RK_ERR_NO_DEVICE;                       // beyond the kMaxDevices the library keeps state for
+    if ((uintptr_t)record & (RK_FIN_STATUS_BYTES - 1)) return RK_ERR_BAD_DIMS;
+    slot->store(static_cast<unsigned*>(record), std::memory_order_relaxed);
+    return RK_OK;
+}
+
 }  // extern "C"

@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import attention_shift, pointwise
+from . import attention_shift, fin_status, pointwise
 
 __all__ = [
     "DistEnv", "init_distributed", "shard_range", "wrap_ddp", "make_optimizer", "train_step",
@@ -130,7 +130,8 @@ def make_optimizer(model, lr=0.01, lr_shift_mult=0.01, kind="adam", momentum=0.9
 
 def train_step(model, optimizer, clips, labels, criterion=None):
     """zero_grad -> forward -> CE -> backward (+ DDP all-reduce) -> step
-    (scripts/example_finetune.py:85-97)."""
+    (scripts/example_finetune.py:85-97).  Raises RubiksHipError when an in-launch finalizer of this or the previous step gave
+    up (fin_status.poll: no host wait; every rank looks at its own device only)."""
     criterion = criterion or nn.functional.cross_entropy
     optimizer.zero_grad(set_to_none=True)
     bf16_step = (clips.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
@@ -142,6 +143,7 @@ def train_step(model, optimizer, clips, labels, criterion=None):
         loss = criterion(out, labels)
         loss.backward()
     optimizer.step()
+    fin_status.poll()
     return loss
 
 

@@ -12,7 +12,7 @@ Training forward: 12 B/elem (stats pass + normalise pass), backward: 20 B/elem, 
 import torch
 import torch.nn.functional as F
 
-from . import _native, config
+from . import _native, config, fin_status
 
 __all__ = ["bn_relu", "bn_relu_skip", "bn_relu_tshift_skip", "bn_relu_shift2d", "fused_bn_enabled"]
 
@@ -147,6 +147,7 @@ class _BNReLUTShiftTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, taps, running_mean, running_var, momentum, eps, n_segment, counter_ptr, stats=None):
         L = _native.lib()
+        fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
         dev = x.device
@@ -180,6 +181,7 @@ class _BNReLUTShiftTrain(torch.autograd.Function):
     def backward(ctx, gy, dskip=None):
         x, weight, bias, taps32, save_mean, save_invstd, ab = ctx.saved_tensors
         L = _native.lib()
+        fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
         S = ctx.n_segment
@@ -244,6 +246,7 @@ class _BNReLUTShiftForkTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, taps, running_mean, running_var, momentum, eps, n_segment, counter_ptr, stats=None):
         L = _native.lib()
+        fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
         dev = x.device
@@ -280,6 +283,7 @@ class _BNReLUTShiftForkTrain(torch.autograd.Function):
     def backward(ctx, gy, gxs):
         x, weight, bias, taps32, save_mean, save_invstd, ab = ctx.saved_tensors
         L = _native.lib()
+        fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
         S = ctx.n_segment
@@ -348,6 +352,7 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
     def forward(ctx, z, weight, bias, shift, running_mean, running_var, momentum, eps, counter_ptr, normalize_grad, stats=None,
                 stride=(1, 1), padding=(0, 0)):
         L = _native.lib()
+        fin_status.ensure(z.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = z.shape
         P = H * W
         dev = z.device
@@ -386,6 +391,7 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
     def backward(ctx, gy):
         z, weight, bias, shift, save_mean, save_invstd, ab, abmi = ctx.saved_tensors
         L = _native.lib()
+        fin_status.ensure(z.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = z.shape
         P = H * W
         dev = z.device

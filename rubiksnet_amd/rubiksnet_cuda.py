@@ -20,7 +20,7 @@ torch::zeros per call (rubiks.cpp:295-299); failures raise instead of exit()ing.
 """
 import torch
 
-from . import _native
+from . import _native, fin_status
 
 __all__ = [
     "rubiks2d_forward",
@@ -98,6 +98,7 @@ def _backward3d(dtype, sfx, input, shift, output_grad, strides, paddings, input_
     s, p = _ints(strides, 3, "strides"), _ints(paddings, 3, "paddings")
     N, T, C, H, W = input.shape
     L = _native.lib()
+    fin_status.ensure(dev)          # a finalizer of this launch that gives up says so in the device's record
     want = (N, L.rk_out_len(T, s[0], p[0]), C, L.rk_out_len(H, s[1], p[1]), L.rk_out_len(W, s[2], p[2]))
     if tuple(output_grad.shape) != want:
         raise RuntimeError("output_grad has shape %s, expected %s" % (tuple(output_grad.shape), want))
@@ -196,6 +197,7 @@ def rubiks2d_backward(upstream_grad, input, shift, strides, paddings, normalize_
     s, p = _ints(strides, 2, "strides"), _ints(paddings, 2, "paddings")
     N, C, H, W = input.shape
     L = _native.lib()
+    fin_status.ensure(dev)          # a finalizer of this launch that gives up says so in the device's record
     want = (N, C, L.rk_out_len(H, s[0], p[0]), L.rk_out_len(W, s[1], p[1]))
     if tuple(upstream_grad.shape) != want:
         raise RuntimeError("upstream_grad has shape %s, expected %s" % (tuple(upstream_grad.shape), want))
@@ -257,6 +259,7 @@ def rubiks_shift_3d_backward_bn_float(input, abmi, shift, output_grad, strides, 
     s, p = _ints(strides, 3, "strides"), _ints(paddings, 3, "paddings")
     N, T, C, H, W = input.shape
     L = _native.lib()
+    fin_status.ensure(dev)          # a finalizer of this launch that gives up says so in the device's record
     want = (N, L.rk_out_len(T, s[0], p[0]), C, L.rk_out_len(H, s[1], p[1]), L.rk_out_len(W, s[2], p[2]))
     if tuple(output_grad.shape) != want or input_grad.shape != input.shape:
         raise RuntimeError("output_grad / input_grad have the wrong shape")

@@ -23,7 +23,7 @@ import logging
 
 import torch
 
-from . import _native, config, rubiksnet_cuda
+from . import _native, config, fin_status, rubiksnet_cuda
 from .fused_bn import _count_batch
 
 __all__ = ["fused_train_block", "take_stats", "bn_relu_from_stats", "stats_fallbacks"]
@@ -278,6 +278,7 @@ class _FusedTrainBlock(torch.autograd.Function):
         dwse1 = dwse2 = None
         L = _native.lib()
         dev = x.device
+        fin_status.ensure(dev)             # the shift backward's in-launch finalizers: a give-up lands in the device's record
         Fr, Cin, H, W, Cmid, Cout, Ho, Wo = plan.Fr, plan.Cin, plan.H, plan.W, plan.Cmid, plan.Cout, plan.Ho, plan.Wo
         P, Po = H * W, Ho * Wo
         s3, pd = [1, plan.stride, plan.stride], [0, 0, 0]
