@@ -38,12 +38,13 @@
  *     on the CURRENT device of the calling thread (hipGetDevice); the Python layer sets it from the tensors' device.
  *   - environment switches, each read once per process:
  *       RK_SHIFT_KERNELS = auto | column | generic selects which kernel families the shift operators may use
- *         (rk_common.hpp; every family is bit-identical for y and d(x), tests/test_fallback_paths_gpu.py);
+ *         (rk_common.hpp; 3-D: rk3d_plan.hpp plan3d::plan, rk_debug_3d_plan shows the choice; every family is bit-identical
+ *         for y and d(x), tests/test_fallback_paths_gpu.py);
  *         RK_FORCE_GENERIC=1 is the older spelling of `generic`;
  *       RK_PW2 = 1 | 0 | 2, RK_PW3 = 1 | 0, RK_PW4 = 1 | 0 | 2: the fp32 1x1 kernel generations (rk_pw.hip: plan_gemm;
  *         rk_debug_pw_gemm_plan shows the choice);
  *       RK_SLAB14 = 1 | 0: the slab kernels on 14x14 planes for the backward too / for nothing (unset: forward only;
- *         rk3d_slab.hip);
+ *         rk3d_plan.hpp plan3d::plan, rk_debug_3d_plan);
  *       RK_BN_FLAT16 = 0: the 4-element BatchNorm sweep for 16-bit storage too; RK_BN_STATS_FUSED = 0: BatchNorm statistics
  *         as a statistics kernel + a finisher kernel (rk_bn.hip).
  */
@@ -115,6 +116,16 @@ int rk3d_debug_finalize_only_status_f32(void* ws, size_t ws_bytes, int C, int pa
 int rk_debug_pw_gemm_plan(int F, int K, int M, int P, int a_is_mk, int aligned, int epi, int res, int pro, int ma, int pw2,
                           int pw3, int pw4, int cus, int* out);
 int rk_debug_pw_wgrad_plan(int F, int K, int M, int P, int pw2);
+/* the RubiksShift3D kernel choice (rk3d_plan.hpp: plan3d::plan) with explicit switches and one alignment bit per operand, no
+ * device call.  form: 0 forward, 1 backward (want_gx / want_gshift; two_phase: rk3d_backward_partials_f32), 2 rk3d_forward_bn_f32,
+ * 3 rk3d_backward_bn_f32; elem_size 4 / 8; aligned (16 bytes): 1 x / z, 2 y (forward) or gy, 4 gx / dz, 8 the BatchNorm pack;
+ * shift_kernels: 0 auto, 1 column, 2 generic (RK_SHIFT_KERNELS); slab14: -1 unset, 0, 1 (RK_SLAB14).  Returns the status the
+ * call would have as far as it does not depend on pointers.  out[30]: launches, P (partials per channel and sum: the workspace
+ * holds [C][3 or 5][P]), whether a separate finalize launch follows, then per launch (3 x 9): family (the enum of
+ * rk3d_plan.hpp), the 5 variant parameters its launcher switches on, grid, block, dynamic LDS bytes. */
+int rk_debug_3d_plan(int form, int elem_size, int N, int T, int C, int H, int W, int sT, int sH, int sW, int pT, int pH, int pW,
+                     int quantize, int want_gx, int want_gshift, int two_phase, int aligned, int shift_kernels, int slab14,
+                     int* out);
 
 /* ------------------------------------------------------------------------- 3D
  * Replaces rubiks_shift_3d_forward<T>  (cuda_src/rubiks.cpp:181-253) + functor

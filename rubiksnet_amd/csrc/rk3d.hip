@@ -1,18 +1,12 @@
 // rk3d.hip -- C-ABI entry points of the RubiksShift3D operator (include/rubiks_hip.h).
 // Host glue restating cuda_src/rubiks.cpp:161-379 (shape math, dispatch) without ATen:
 // caller-owned buffers and workspace, explicit stream, error codes instead of exit().
-#include "rk3d_generic.hpp"
-#include "rk3d_dma.hpp"
-#include "rk3d_plane.hpp"
-#include "rk3d_tile.hpp"
-#include "rk3d_translate.hpp"
-#include "rk3d_stride2.hpp"
-#include "rk3d_column.hpp"
-#include "rk3d_slab.hpp"
+#include "rk3d_plan.hpp"
 
 #include <type_traits>
 
 using namespace rk;
+using namespace rk::plan3d;
 
 namespace {
 
@@ -33,46 +27,96 @@ int make_dims(Dims3& d, int N, int T, int C, int H, int W, int sT, int sH, int s
     return RK_OK;
 }
 
-void set_group(Dims3& d, int plane_elems) {
-    d.E = pow2_at_least(plane_elems, kWave, kBlock);
-    d.logE = (d.E == 64) ? 6 : (d.E == 128 ? 7 : 8);
+// the process's switches, read once: RK_SHIFT_KERNELS (rk_common.hpp) and RK_SLAB14 (rk3d_plan.hpp)
+const Switches& env_switches() {
+    static const Switches sw = [] {
+        const char* e = getenv("RK_SLAB14");
+        return Switches{shift_kernels(), e ? (e[0] == '1' ? 1 : 0) : -1};
+    }();
+    return sw;
 }
+// the Aligned bit `bit` of an operand (NULL: the call does not have it)
+int al(const void* p, int bit) { return ((uintptr_t)p & 15) == 0 ? bit : 0; }
 
-unsigned grid_for(const Dims3& d, long long planes) {
-    const int per_block = kBlock / d.E;
-    return (unsigned)((planes + per_block - 1) / per_block);
+// the operands of a call, by the names the launchers use
+template <typename T> struct Ops {
+    const T* x; const T* shift; const T* gy; T* y; T* gx; T* gshift; T* ws;
+    int normalize; T t_factor;
+    dma3d::BnFuse bn;
+};
+
+// runs one planned launch
+template <typename T>
+void run(const Launch& l, const Dims3& d, int P, const Ops<T>& o, hipStream_t stream) {
+    const Cfg3& c = l.c;
+    if constexpr (std::is_same<T, float>::value) {
+        const bool negate = c.v[0];                                    // forward / d(x)-only families
+        const float* src = negate ? o.gy : o.x;
+        float* dst = negate ? o.gx : o.y;
+        const bool bwd = l.family == kDmaBwd || l.family == kTileBwd || l.family == kSlabBwd || l.family == kS2Bwd ||
+                         l.family == kSlabS2Bwd || l.family == kColBwd;
+        float* gx = bwd && c.v[0] ? o.gx : nullptr;                    // (the d(shift) half behind a translation writes no d(x))
+        const dma3d::Fin3 fin = bwd && c.v[1] ? dma3d::make_fin3(o.ws, (int)c.grid - d.C, o.gshift, o.normalize, o.t_factor) : dma3d::Fin3{};
+        switch (l.family) {
+            case kPlane: return plane3d::launch(c, l.g.plane, src, o.shift, dst, o.bn.abmi, stream);
+            case kDmaInterp:
+                if (c.v[1]) return dma3d::launch_forward_bn(c, l.g.band, src, o.shift, dst, o.bn.abmi, stream);
+                if (negate) return dma3d::launch_interp<true>(c, l.g.band, src, o.shift, dst, stream);
+                return dma3d::launch_interp<false>(c, l.g.band, src, o.shift, dst, stream);
+            case kTileInterp: return tile3d::launch_interp(c, d, src, o.shift, dst, o.bn.abmi, stream);
+            case kSlabInterp: return slab3d::launch_interp(c, l.g.slab, d, src, o.shift, dst, stream);
+            case kXlate: return xlate3d::launch(c, l.g.gen, src, o.shift, dst, stream);
+            case kS2Fwd: return s2::launch_forward(c, l.g.s2, o.x, o.shift, o.y, o.bn.abmi, stream);
+            case kSlabS2Fwd: return slab3d::launch_fwd_s2(c, l.g.slab2, d, o.x, o.shift, o.y, stream);
+            case kDmaBwd: return dma3d::launch_bwd(c, l.g.band, d, o.x, o.shift, o.gy, gx, o.ws, fin, o.bn, stream);
+            case kTileBwd: return tile3d::launch_bwd(c, d, o.x, o.shift, o.gy, gx, o.ws, fin, o.bn, stream);
+            case kSlabBwd: return slab3d::launch_bwd(c, l.g.slab, d, o.x, o.shift, o.gy, gx, o.ws, fin, stream);
+            case kS2Bwd: return s2::launch_backward(c, l.g.s2, d, o.x, o.shift, o.gy, gx, o.ws, fin, o.bn, stream);
+            case kSlabS2Bwd: return slab3d::launch_bwd_s2(c, l.g.slab2, d, o.x, o.shift, o.gy, gx, o.ws, fin, stream);
+            case kColBwd: return col3d::launch_backward<T>(c, l.g.col, o.x, o.shift, o.gy, gx, o.ws, fin, stream);
+            default: break;
+        }
+    }
+    const dim3 grid(c.grid), block(kBlock);
+    switch (l.family) {
+        case kColFwd: return col3d::launch_forward<T>(c, l.g.col, o.x, o.shift, o.y, stream);
+        case kColBwd: return col3d::launch_backward<T>(c, l.g.col, o.x, o.shift, o.gy, o.gx, o.ws, dma3d::Fin3{}, stream);
+        case kGenFwd:
+            if (c.v[0]) hipLaunchKernelGGL((k3d_forward_generic<T, true>), grid, block, 0, stream, o.x, o.shift, o.y, l.g.gen);
+            else hipLaunchKernelGGL((k3d_forward_generic<T, false>), grid, block, 0, stream, o.x, o.shift, o.y, l.g.gen);
+            return;
+        case kGenBwdX:
+            if (c.v[0]) hipLaunchKernelGGL((k3d_backward_input_generic<T, true>), grid, block, 0, stream, o.shift, o.gy, o.gx, l.g.gen);
+            else hipLaunchKernelGGL((k3d_backward_input_generic<T, false>), grid, block, 0, stream, o.shift, o.gy, o.gx, l.g.gen);
+            return;
+        case kGenBwdS:
+            hipLaunchKernelGGL((k3d_backward_shift_generic<T>), grid, block, 0, stream, o.x, o.shift, o.gy, o.ws, l.g.gen);
+            return;
+        case kFinalize:
+            hipLaunchKernelGGL((k3d_finalize<T>), grid, dim3(finalize_block(P)), 0, stream, (const T*)o.ws, o.gshift, d.C, P,
+                               o.normalize, o.t_factor);
+            return;
+        default: return;
+    }
 }
-
-bool is_s1p0(const Dims3& d) {
-    return d.sT == 1 && d.sH == 1 && d.sW == 1 && d.pT == 0 && d.pH == 0 && d.pW == 0;
+template <typename T>
+int run(const Plan& pl, const Dims3& d, const Ops<T>& o, rk_stream_t stream) {
+    if (pl.rc) return pl.rc;
+    for (int i = 0; i < pl.n; ++i) run<T>(pl.l[i], d, pl.P, o, (hipStream_t)stream);
+    return launch_status();
 }
 
 template <typename T>
 int forward_impl(const T* x, const T* shift, T* y, int N, int Tn, int C, int H, int W, int sT, int sH, int sW,
-                 int pT, int pH, int pW, int quantize, rk_stream_t stream_) {
+                 int pT, int pH, int pW, int quantize, rk_stream_t stream) {
     if (!x || !shift || !y) return RK_ERR_NULL_POINTER;
-    Dims3 d;
-    if (int rc = make_dims(d, N, Tn, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    if constexpr (std::is_same<T, float>::value) {
-        if (!quantize && plane3d::launch_interp<false>(x, shift, y, d, stream)) return launch_status();
-        if (!quantize && dma3d::launch_interp<false>(x, shift, y, d, stream)) return launch_status();
-        const bool p14 = d.H == 14 && d.W == 14;
-        if (!quantize && p14 && slab3d::slab14_on(false) && slab3d::launch_interp(false, x, shift, y, d, stream)) return launch_status();
-        if (!quantize && tile3d::launch_interp<false>(x, shift, y, d, stream)) return launch_status();
-        if (!quantize && !p14 && slab3d::launch_interp(false, x, shift, y, d, stream)) return launch_status();   // small planes
-        if (quantize && xlate3d::launch<false>(x, shift, y, d, stream)) return launch_status();   // plane translation
-        if (!quantize && s2::launch_forward(x, shift, y, d, stream)) return launch_status();       // stride (1,2,2)
-        if (!quantize && slab3d::launch_fwd_s2(x, shift, y, d, stream)) return launch_status();    // stride (1,2,2), 28 -> 14 and 14 -> 7
-    }
-    if (col3d::supported(d, quantize)) return col3d::launch_forward<T>(x, shift, y, d, stream);
-    set_group(d, d.Ho * d.Wo);
-    const unsigned grid = grid_for(d, (long long)d.N * d.To * d.C);
-    if (quantize)
-        hipLaunchKernelGGL((k3d_forward_generic<T, true>), dim3(grid), dim3(kBlock), 0, stream, x, shift, y, d);
-    else
-        hipLaunchKernelGGL((k3d_forward_generic<T, false>), dim3(grid), dim3(kBlock), 0, stream, x, shift, y, d);
-    return launch_status();
+    Call c{};
+    if (int rc = make_dims(c.d, N, Tn, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
+    c.form = kForward; c.elem = (int)sizeof(T); c.quantize = quantize;
+    c.aligned = al(x, kAlX) | al(y, kAlY);
+    Ops<T> o{};
+    o.x = x; o.shift = shift; o.y = y;
+    return run<T>(plan(c, env_switches()), c.d, o, stream);
 }
 
 // `P_out` != nullptr: two-phase use -- stop after the partials (ws[C][3][*P_out]) and report their count instead of
@@ -80,104 +124,24 @@ int forward_impl(const T* x, const T* shift, T* y, int N, int Tn, int C, int H, 
 template <typename T>
 int backward_impl(const T* x, const T* shift, const T* gy, T* gx, T* gshift, int N, int Tn, int C, int H, int W,
                   int sT, int sH, int sW, int pT, int pH, int pW, int normalize_grad, T t_factor, int quantize,
-                  void* ws, size_t ws_bytes, rk_stream_t stream_, int* P_out = nullptr) {
+                  void* ws, size_t ws_bytes, rk_stream_t stream, int* P_out = nullptr) {
     if (!shift || !gy || (!gx && !gshift)) return RK_ERR_NULL_POINTER;
     if (gshift && !x) return RK_ERR_NULL_POINTER;
-    Dims3 d;
-    if (int rc = make_dims(d, N, Tn, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
+    Call c{};
+    if (int rc = make_dims(c.d, N, Tn, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
     if (gshift) {
         const size_t need = rk3d_backward_workspace_bytes(N, Tn, C, H, W, sT, sH, sW, pT, pH, pW, (int)sizeof(T));
         if (!ws || ws_bytes < need) return RK_ERR_WORKSPACE;
     }
-    // row-sum of the P partials per channel + K5 -- or, in two-phase use, just report P
-    auto finish = [&](int P) {
-        if (P_out) { *P_out = P; return launch_status(); }
-        hipLaunchKernelGGL((k3d_finalize<T>), dim3(d.C), dim3(finalize_block(P)), 0, stream, (const T*)ws, gshift, d.C, P,
-                           normalize_grad, t_factor);
-        return launch_status();
-    };
-    if constexpr (std::is_same<T, float>::value) {
-        // quantize: d(x) is a plane translation; d(shift) does not depend on quantize (K2 takes the fractional
-        // shift, rubiks.cpp:324-358), so it comes from the streaming backward without its d(x) half
-        if (quantize && gx && gshift && !P_out) {                       // both gradients, one launch (rk3d_dma.hpp QUANT)
-            if (dma3d::launch_bwd(x, shift, gy, gx, gshift, (float*)ws, d, normalize_grad, t_factor, stream, true))
-                return launch_status();
-        }
-        if (quantize && gx && xlate3d::launch<true>(gy, shift, gx, d, stream)) {
-            if (!gshift) return launch_status();
-            gx = nullptr;
-            int P = dma3d::launch_bwd(x, shift, gy, nullptr, P_out ? nullptr : gshift, (float*)ws, d, normalize_grad,
-                                      t_factor, stream);
-            if (!P) P = tile3d::launch_bwd(x, shift, gy, nullptr, P_out ? nullptr : gshift, (float*)ws, d, normalize_grad,
-                                           t_factor, stream);
-            if (P) {
-                if (P_out) *P_out = P;
-                return launch_status();
-            }
-        }
-        if (!quantize && gshift) {
-            // one-call form: row-sum + K5 happen inside the launch; two-phase form: plain partials
-            if (const int P = dma3d::launch_bwd(x, shift, gy, gx, P_out ? nullptr : gshift, (float*)ws, d, normalize_grad,
-                                                t_factor, stream)) {
-                if (P_out) *P_out = P;
-                return launch_status();
-            }
-            {   // 14x14: the tile kernels (or, RK_SLAB14=1, the slab kernels first); other small planes: the slab kernels
-                const bool p14 = d.H == 14 && d.W == 14;
-                float* gs = P_out ? nullptr : gshift;
-                int P = 0;
-                if (p14 && slab3d::slab14_on(true)) P = slab3d::launch_bwd(x, shift, gy, gx, gs, (float*)ws, d, normalize_grad, t_factor, stream);
-                if (!P) P = tile3d::launch_bwd(x, shift, gy, gx, gs, (float*)ws, d, normalize_grad, t_factor, stream);
-                if (!P && !p14) P = slab3d::launch_bwd(x, shift, gy, gx, gs, (float*)ws, d, normalize_grad, t_factor, stream);
-                if (P) {
-                    if (P_out) *P_out = P;
-                    return launch_status();
-                }
-            }
-            if (const int P = s2::launch_backward(x, shift, gy, gx, P_out ? nullptr : gshift, (float*)ws, d, normalize_grad,
-                                                  t_factor, stream)) {      // stride (1,2,2)
-                if (P_out) *P_out = P;
-                return launch_status();
-            }
-            if (const int P = slab3d::launch_bwd_s2(x, shift, gy, gx, P_out ? nullptr : gshift, (float*)ws, d, normalize_grad,
-                                                    t_factor, stream)) {    // stride (1,2,2), 28 -> 14 and 14 -> 7
-                if (P_out) *P_out = P;
-                return launch_status();
-            }
-        } else if (!quantize && gx) {
-            if (plane3d::launch_interp<true>(gy, shift, gx, d, stream)) return launch_status();
-            if (dma3d::launch_interp<true>(gy, shift, gx, d, stream)) return launch_status();
-            const bool p14 = d.H == 14 && d.W == 14;
-            if (p14 && slab3d::slab14_on(false) && slab3d::launch_interp(true, gy, shift, gx, d, stream)) return launch_status();
-            if (tile3d::launch_interp<true>(gy, shift, gx, d, stream)) return launch_status();
-            if (!p14 && slab3d::launch_interp(true, gy, shift, gx, d, stream)) return launch_status();
-        }
-    }
-    if (gshift && col3d::supported(d, quantize)) {
-        // one-call form (fp32): row-sum + K5 inside the launch; two-phase form / fp64: partials, then k3d_finalize
-        const int P = col3d::launch_backward<T>(x, shift, gy, gx, (T*)ws, d, stream, P_out ? nullptr : gshift, normalize_grad,
-                                                t_factor);
-        return P < 0 ? launch_status() : finish(P);
-    }
-
-    if (gx) {       // rubiks.cpp:363-376
-        set_group(d, d.H * d.W);
-        const unsigned grid = grid_for(d, (long long)d.N * d.T * d.C);
-        if (quantize)
-            hipLaunchKernelGGL((k3d_backward_input_generic<T, true>), dim3(grid), dim3(kBlock), 0, stream, shift, gy,
-                               gx, d);
-        else
-            hipLaunchKernelGGL((k3d_backward_input_generic<T, false>), dim3(grid), dim3(kBlock), 0, stream, shift,
-                               gy, gx, d);
-    }
-    if (gshift) {   // rubiks.cpp:324-358
-        set_group(d, d.Ho * d.Wo);
-        hipLaunchKernelGGL((k3d_backward_shift_generic<T>), dim3(grid_for(d, (long long)d.N * d.To * d.C)),
-                           dim3(kBlock), 0, stream, x, shift, gy, (T*)ws, d);
-        return finish(d.N * d.To);
-    }
-    return launch_status();
+    c.form = kBackward; c.elem = (int)sizeof(T); c.quantize = quantize;
+    c.gx = gx; c.gshift = gshift; c.two_phase = P_out;
+    c.aligned = al(x, kAlX) | al(gy, kAlY) | al(gx, kAlGx);
+    const Plan pl = plan(c, env_switches());
+    Ops<T> o{};
+    o.x = x; o.shift = shift; o.gy = gy; o.gx = gx; o.gshift = gshift; o.ws = (T*)ws;
+    o.normalize = normalize_grad; o.t_factor = t_factor;
+    if (P_out) *P_out = pl.P;
+    return run<T>(pl, c.d, o, stream);
 }
 
 }  // namespace
@@ -204,18 +168,16 @@ size_t rk3d_backward_workspace_bytes(int N, int T, int C, int H, int W, int sT, 
 // Both return RK_ERR_UNSUPPORTED (no launch, nothing touched) when no fused kernel covers the configuration; the caller
 // then normalises with rk_bn_apply_affine_f32 and calls the plain entry points.
 int rk3d_forward_bn_f32(const float* z, const float* abmi, const float* shift, float* y, int N, int T, int C, int H,
-                        int W, int sT, int sH, int sW, int pT, int pH, int pW, int quantize, rk_stream_t stream_) {
+                        int W, int sT, int sH, int sW, int pT, int pH, int pW, int quantize, rk_stream_t stream) {
     if (!z || !abmi || !shift || !y) return RK_ERR_NULL_POINTER;
-    Dims3 d;
-    if (int rc = make_dims(d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
-    if (quantize) return RK_ERR_UNSUPPORTED;
-    hipStream_t stream = (hipStream_t)stream_;
-    const float4* pk = reinterpret_cast<const float4*>(abmi);
-    if (plane3d::launch_forward_bn(z, shift, y, pk, d, stream)) return launch_status();
-    if (dma3d::launch_forward_bn(z, shift, y, pk, d, stream)) return launch_status();
-    if (tile3d::launch_forward_bn(z, shift, y, pk, d, stream)) return launch_status();
-    if (s2::launch_forward_bn(z, shift, y, pk, d, stream)) return launch_status();
-    return RK_ERR_UNSUPPORTED;
+    Call c{};
+    if (int rc = make_dims(c.d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
+    c.form = kForwardBn; c.elem = 4; c.quantize = quantize;
+    c.aligned = al(z, kAlX) | al(y, kAlY) | al(abmi, kAlBn);
+    Ops<float> o{};
+    o.x = z; o.shift = shift; o.y = y;
+    o.bn.abmi = reinterpret_cast<const float4*>(abmi);
+    return run<float>(plan(c, env_switches()), c.d, o, stream);
 }
 size_t rk3d_backward_bn_workspace_bytes(int N, int T, int C, int H, int W, int sT, int sH, int sW, int pT, int pH, int pW) {
     // five partials per (channel, column-band) instead of three, as 16-byte granule pairs
@@ -224,23 +186,20 @@ size_t rk3d_backward_bn_workspace_bytes(int N, int T, int C, int H, int W, int s
 int rk3d_backward_bn_f32(const float* z, const float* abmi, const float* shift, const float* gy, float* dz, float* gshift,
                          float* k12, float* dgamma, float* dbeta, int N, int T, int C, int H, int W, int sT, int sH,
                          int sW, int pT, int pH, int pW, int normalize_grad, float t_factor, int quantize, void* ws,
-                         size_t ws_bytes, rk_stream_t stream_) {
+                         size_t ws_bytes, rk_stream_t stream) {
     if (!z || !abmi || !shift || !gy || !dz || !gshift || !k12 || !dgamma || !dbeta) return RK_ERR_NULL_POINTER;
-    Dims3 d;
-    if (int rc = make_dims(d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
+    Call c{};
+    if (int rc = make_dims(c.d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
     if (!ws || ws_bytes < rk3d_backward_bn_workspace_bytes(N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return RK_ERR_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
-    dma3d::BnFuse bn;
-    bn.abmi = reinterpret_cast<const float4*>(abmi);
-    bn.k12 = k12; bn.dgamma = dgamma; bn.dbeta = dbeta;
-    bn.inv_count = (float)(1.0 / ((double)N * T * H * W));
-    if (dma3d::launch_bwd_bn(z, shift, gy, dz, gshift, (float*)ws, d, normalize_grad, t_factor, quantize, bn, stream))
-        return launch_status();
-    if (!quantize && tile3d::launch_bwd_bn(z, shift, gy, dz, gshift, (float*)ws, d, normalize_grad, t_factor, bn, stream))
-        return launch_status();
-    if (!quantize && s2::launch_backward_bn(z, shift, gy, dz, gshift, (float*)ws, d, normalize_grad, t_factor, bn, stream))
-        return launch_status();
-    return RK_ERR_UNSUPPORTED;
+    c.form = kBackwardBn; c.elem = 4; c.quantize = quantize; c.gx = c.gshift = true;
+    c.aligned = al(z, kAlX) | al(gy, kAlY) | al(dz, kAlGx) | al(abmi, kAlBn);
+    Ops<float> o{};
+    o.x = z; o.shift = shift; o.gy = gy; o.gx = dz; o.gshift = gshift; o.ws = (float*)ws;
+    o.normalize = normalize_grad; o.t_factor = t_factor;
+    o.bn.abmi = reinterpret_cast<const float4*>(abmi);
+    o.bn.k12 = k12; o.bn.dgamma = dgamma; o.bn.dbeta = dbeta;
+    o.bn.inv_count = (float)(1.0 / ((double)N * T * H * W));
+    return run<float>(plan(c, env_switches()), c.d, o, stream);
 }
 
 int rk3d_forward_f32(const float* x, const float* shift, float* y, int N, int T, int C, int H, int W, int sT,
@@ -295,20 +254,40 @@ int rk3d_debug_finalize_only_status_f32(void* ws, size_t ws_bytes, int C, int pa
     if (C <= 0 || partials <= 0) return RK_ERR_BAD_DIMS;
     if ((uintptr_t)record & (RK_FIN_STATUS_BYTES - 1)) return RK_ERR_BAD_DIMS;
     if (ws_bytes < (size_t)C * 3 * partials * 16) return RK_ERR_WORKSPACE;
-    dma3d::Fin3 fin{};
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    dma::fin_arm(fin.f);
+    dma3d::Fin3 fin = dma3d::make_fin3(ws, 0, gshift, normalize_grad, t_factor);
     fin.f.status = static_cast<unsigned*>(record);
-    fin.f.producers = 0;
-    fin.gshift = gshift;
-    fin.normalize = normalize_grad;
-    fin.t_factor = t_factor;
     hipLaunchKernelGGL(k3d_debug_finalize_only, dim3((unsigned)C), dim3(kWave), 0, (hipStream_t)stream, fin, C, partials);
     return launch_status();
 }
 int rk3d_debug_finalize_only_f32(void* ws, size_t ws_bytes, int C, int partials, float* gshift, int normalize_grad,
                                  float t_factor, rk_stream_t stream) {
     return rk3d_debug_finalize_only_status_f32(ws, ws_bytes, C, partials, gshift, normalize_grad, t_factor, nullptr, stream);
+}
+
+
+// Test hook: the planner with explicit switches and alignment bits (no device call).  form: 0 forward, 1 backward,
+// 2 rk3d_forward_bn_f32, 3 rk3d_backward_bn_f32; shift_kernels: 0 auto, 1 column, 2 generic; slab14: -1 unset, 0, 1;
+// aligned: 1 x / z, 2 y or gy, 4 gx / dz, 8 the BN pack.  out[0] = launches, out[1] = P, out[2] = a separate finalize
+// follows, then 9 ints per launch: family (rk3d_plan.hpp), its variant x 5, grid, block, dynamic LDS bytes.  Returns the
+// call's status as far as it does not depend on pointers.
+int rk_debug_3d_plan(int form, int elem_size, int N, int T, int C, int H, int W, int sT, int sH, int sW, int pT, int pH, int pW,
+                     int quantize, int want_gx, int want_gshift, int two_phase, int aligned, int shift_kernels, int slab14,
+                     int* out) {
+    Call c{};
+    if (int rc = make_dims(c.d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
+    c.form = (Form)form; c.elem = elem_size; c.quantize = quantize;
+    c.gx = want_gx; c.gshift = want_gshift; c.two_phase = two_phase; c.aligned = aligned;
+    const Plan pl = plan(c, Switches{(ShiftKernels)shift_kernels, slab14});
+    if (!out) return pl.rc;
+    out[0] = pl.n; out[1] = pl.P; out[2] = pl.finalize;
+    for (int i = 0; i < 3; ++i) {
+        const Launch& l = pl.l[i];
+        int* o = out + 3 + 9 * i;
+        o[0] = l.family;
+        for (int k = 0; k < 5; ++k) o[1 + k] = l.c.v[k];
+        o[6] = (int)l.c.grid; o[7] = i >= pl.n ? 0 : l.family == kFinalize ? finalize_block(pl.P) : kBlock; o[8] = (int)l.c.lds;
+    }
+    return pl.rc;
 }
 
 }  // extern "C"

@@ -360,10 +360,8 @@ __global__ __launch_bounds__(kBlock) void k3d_backward_column(const T* __restric
 }
 
 // ----------------------------------------------------------------------------------- host side
-inline bool supported(const Dims3& d, int quantize) {
-    return column_kernels_on() && !quantize && d.sT == 1 && d.pT == 0;
-}
-
+// geometry for plan3d (rk3d_plan.hpp; it has checked the switches, quantize and the temporal stride / padding) and launchers,
+// which run the configuration they are given
 // plane_elems: the plane the threads index (output plane for forward, input plane for backward)
 inline CDims make_cdims(const Dims3& d, int plane_elems) {
     CDims cd;
@@ -383,54 +381,29 @@ inline unsigned grid_of(const CDims& cd) {
     return (unsigned)((groups + per_block - 1) / per_block);
 }
 
-// 16-byte accesses on the streamed planes: fp32, plane a multiple of 4 elements, 16-byte aligned tensors
-template <typename T> inline bool vec_ok(int plane_elems, const void* a, const void* b) {
-    return std::is_same<T, float>::value && plane_elems % 4 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0;
+// v[2] = kM
+template <typename T>
+inline void launch_forward(const Cfg3& c, const CDims& cd, const T* x, const T* shift, T* y, hipStream_t stream) {
+    if (c.v[2] == 1) hipLaunchKernelGGL((k3d_forward_column<T, 1>), dim3(c.grid), dim3(kBlock), 0, stream, x, shift, y, cd);
+    else hipLaunchKernelGGL((k3d_forward_column<T, 4>), dim3(c.grid), dim3(kBlock), 0, stream, x, shift, y, cd);
 }
 
+// v = WRITE_GX, FUSED (fp32: row-sum + K5 inside the launch, ws = granule pairs; else plain partials ws[C][3][P] for
+// k3d_finalize / the two-phase ABI), kM, SINGLE, VEC (16-byte accesses on the streamed planes, kM = 4 only); P = N * nchunks
 template <typename T>
-inline int launch_forward(const T* x, const T* shift, T* y, const Dims3& d, hipStream_t stream) {
-    const CDims cd = make_cdims(d, d.Ho * d.Wo);
-    if (cd.M == 1)
-        hipLaunchKernelGGL((k3d_forward_column<T, 1>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, x, shift, y, cd);
-    else
-        hipLaunchKernelGGL((k3d_forward_column<T, 4>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, x, shift, y, cd);
-    return launch_status();
-}
-
-// returns P (partials per channel).  gshift != nullptr (fp32): row-sum + K5 inside the launch (ws = granule pairs);
-// nullptr: plain partials ws[C][3][P] for k3d_finalize / the two-phase ABI
-template <typename T>
-inline int launch_backward(const T* x, const T* shift, const T* gy, T* gx, T* ws, const Dims3& d,
-                           hipStream_t stream, T* gshift = nullptr, int normalize = 0, T t_factor = 1) {
-    const CDims cd = make_cdims(d, d.H * d.W);
-    const bool single = d.sH >= 2 && d.sW >= 2;
-    const bool vec = cd.M == 4 && vec_ok<T>(d.H * d.W, x, gx);
-    dma3d::Fin3 fin{};
-    bool fused = false;
-    if constexpr (std::is_same<T, float>::value) {
-        if (gshift && streaming_kernels_on()) {
-            fused = true;
-            fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-            dma::fin_arm(fin.f);
-            fin.f.producers = (int)grid_of(cd);
-            fin.gshift = gshift;
-            fin.normalize = normalize;
-            fin.t_factor = t_factor;
-        }
-    }
-    const unsigned grid = grid_of(cd) + (fused ? (unsigned)d.C : 0u);
+inline void launch_backward(const Cfg3& c, const CDims& cd, const T* x, const T* shift, const T* gy, T* gx, T* ws,
+                            const dma3d::Fin3& fin, hipStream_t stream) {
+    const bool gxw = c.v[0], fused = c.v[1], single = c.v[3], vec = c.v[4];
 #define RK_COL_BWD(GX, MM, SG, VC) do { \
         if constexpr (std::is_same<T, float>::value) { \
-            if (fused) { hipLaunchKernelGGL((k3d_backward_column<T, GX, MM, SG, VC, true>), dim3(grid), dim3(kBlock), 0, stream, x, shift, gy, gx, ws, cd, fin); break; } \
+            if (fused) { hipLaunchKernelGGL((k3d_backward_column<T, GX, MM, SG, VC, true>), dim3(c.grid), dim3(kBlock), 0, stream, x, shift, gy, gx, ws, cd, fin); break; } \
         } \
-        hipLaunchKernelGGL((k3d_backward_column<T, GX, MM, SG, VC>), dim3(grid), dim3(kBlock), 0, stream, x, shift, gy, gx, ws, cd, fin); } while (0)
+        hipLaunchKernelGGL((k3d_backward_column<T, GX, MM, SG, VC>), dim3(c.grid), dim3(kBlock), 0, stream, x, shift, gy, gx, ws, cd, fin); } while (0)
 #define RK_COL_SG(GX, MM, VC) do { if (single) RK_COL_BWD(GX, MM, true, VC); else RK_COL_BWD(GX, MM, false, VC); } while (0)
-    if (gx) { if (cd.M == 1) RK_COL_SG(true, 1, false); else if (vec) RK_COL_SG(true, 4, true); else RK_COL_SG(true, 4, false); }
-    else { if (cd.M == 1) RK_COL_SG(false, 1, false); else if (vec) RK_COL_SG(false, 4, true); else RK_COL_SG(false, 4, false); }
+    if (gxw) { if (c.v[2] == 1) RK_COL_SG(true, 1, false); else if (vec) RK_COL_SG(true, 4, true); else RK_COL_SG(true, 4, false); }
+    else { if (c.v[2] == 1) RK_COL_SG(false, 1, false); else if (vec) RK_COL_SG(false, 4, true); else RK_COL_SG(false, 4, false); }
 #undef RK_COL_SG
 #undef RK_COL_BWD
-    return fused ? -(d.N * cd.nchunks) : d.N * cd.nchunks;       // negative: finished inside the launch
 }
 
 }  // namespace col3d

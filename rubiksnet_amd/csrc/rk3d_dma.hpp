@@ -396,6 +396,17 @@ struct Fin3 {
     int normalize;
     float t_factor;
 };
+// armed for one launch: blocks [0, producers) publish to ws, the C blocks behind them finalize into gshift
+inline Fin3 make_fin3(void* ws, int producers, float* gshift, int normalize, float t_factor) {
+    Fin3 fin{};
+    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
+    fin_arm(fin.f);
+    fin.f.producers = producers;
+    fin.gshift = gshift;
+    fin.normalize = normalize;
+    fin.t_factor = t_factor;
+    return fin;
+}
 // training fusion (BN above): what the shift backward needs of bn2 and where bn2's backward constants go
 struct BnFuse {
     const float4* abmi;           // [C] (a, b, mean, invstd)
@@ -530,113 +541,81 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side: launchers.
-// false = shape not handled by the DMA kernels
-inline bool make_bdims(BDims& b, const Dims3& d, bool backward = false) {
-    const bool s1p0 = d.sT == 1 && d.sH == 1 && d.sW == 1 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || d.W % 4 != 0 || d.W < 4 || !streaming_kernels_on()) return false;
-    b.N = d.N; b.T = d.T; b.C = d.C; b.H = d.H; b.W = d.W; b.W4 = d.W / 4;
-    return choose_bands(b, backward);
+// Host side: geometry for plan3d (rk3d_plan.hpp; it has checked stride 1 / pad 0, W % 4 == 0, W >= 4, alignment and the
+// switches) and launchers, which run the configuration they are given.
+inline BDims band_dims(const Dims3& d) { return BDims{d.N, d.T, d.C, d.H, d.W, d.W / 4, 0, 0}; }
+
+// forward / d(x)-only: 2 planes in flight per column (1 and 3 measured within 1 %).  false = not for these kernels
+constexpr int kDepth = 2;
+inline bool interp_geometry(BDims& b, Cfg3& c, const Dims3& d) {
+    b = band_dims(d);
+    if (!choose_bands(b) || interp_ring_bytes(b, kDepth) > 64 * 1024) return false;
+    c.v[2] = rounds_of(b);
+    c.grid = (unsigned)(b.N * b.C * b.nbands);
+    c.lds = interp_ring_bytes(b, kDepth);
+    return true;
+}
+// d(shift) (+ d(x)): one gy plane and one x plane in flight (2 / 2 measured within 1 %: the memory system, not latency,
+// bounds it).  c.grid: the producers (a FUSED launch adds C finalizer blocks); P = b.N * b.nbands
+inline bool bwd_geometry(BDims& b, Cfg3& c, const Dims3& d) {
+    b = band_dims(d);
+    if (!choose_bands(b, true) || bwd_ring_bytes(b, 1, 1) > 64 * 1024) return false;
+    c.v[2] = rounds_of(b);
+    c.grid = (unsigned)(b.N * b.C * b.nbands);
+    c.lds = bwd_ring_bytes(b, 1, 1);
+    return true;
 }
 
-template <bool NEGATE, int D, bool BN = false>
-inline void launch_interp_d(const float* src, const float* shift, float* dst, const BDims& b, hipStream_t stream,
-                            const float4* abmi = nullptr) {
-    const size_t lds = interp_ring_bytes(b, D);
-    const dim3 grid((unsigned)(b.N * b.C * b.nbands)), block(kBlock);
-    switch (rounds_of(b)) {
-        case 1: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 1, D, BN>), grid, block, lds, stream, src, shift, dst, b, abmi); break;
-        case 2: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 2, D, BN>), grid, block, lds, stream, src, shift, dst, b, abmi); break;
-        case 3: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 3, D, BN>), grid, block, lds, stream, src, shift, dst, b, abmi); break;
-        default: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 4, D, BN>), grid, block, lds, stream, src, shift, dst, b, abmi); break;
+template <bool NEGATE, bool BN>
+inline void launch_interp_r(const Cfg3& c, const BDims& b, const float* src, const float* shift, float* dst, const float4* abmi,
+                            hipStream_t stream) {
+    const dim3 grid(c.grid), block(kBlock);
+    switch (c.v[2]) {
+        case 1: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 1, kDepth, BN>), grid, block, c.lds, stream, src, shift, dst, b, abmi); break;
+        case 2: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 2, kDepth, BN>), grid, block, c.lds, stream, src, shift, dst, b, abmi); break;
+        case 3: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 3, kDepth, BN>), grid, block, c.lds, stream, src, shift, dst, b, abmi); break;
+        default: hipLaunchKernelGGL((k3d_dma_interp<NEGATE, 4, kDepth, BN>), grid, block, c.lds, stream, src, shift, dst, b, abmi); break;
     }
 }
-
-// forward / d(x)-only; false = not handled here.  2 planes in flight per column (1 and 3 measured within 1 %).
+// v[2] = ROUNDS
 template <bool NEGATE>
-inline bool launch_interp(const float* src, const float* shift, float* dst, const Dims3& d, hipStream_t stream) {
-    constexpr int kDepth = 2;
-    BDims b;
-    if (!make_bdims(b, d) || !aligned16(src) || !aligned16(dst)) return false;
-    if (interp_ring_bytes(b, kDepth) > 64 * 1024) return false;
-    launch_interp_d<NEGATE, kDepth>(src, shift, dst, b, stream);
-    return true;
+inline void launch_interp(const Cfg3& c, const BDims& b, const float* src, const float* shift, float* dst, hipStream_t stream) {
+    launch_interp_r<NEGATE, false>(c, b, src, shift, dst, nullptr, stream);
 }
 // forward of relu(bn(z)) (train_block.py): abmi [C] = (a, b, mean, invstd)
-inline bool launch_forward_bn(const float* z, const float* shift, float* y, const float4* abmi, const Dims3& d,
+inline void launch_forward_bn(const Cfg3& c, const BDims& b, const float* z, const float* shift, float* y, const float4* abmi,
                               hipStream_t stream) {
-    constexpr int kDepth = 2;
-    BDims b;
-    if (!make_bdims(b, d) || !aligned16(z) || !aligned16(y) || !aligned16(abmi)) return false;
-    if (interp_ring_bytes(b, kDepth) > 64 * 1024) return false;
-    launch_interp_d<false, kDepth, true>(z, shift, y, b, stream, abmi);
-    return true;
+    launch_interp_r<false, true>(c, b, z, shift, y, abmi, stream);
 }
 
-template <bool WRITE_GX, int DG, int DX, bool FUSED, bool QUANT = false, bool BN = false>
-inline void launch_bwd_d(const float* x, const float* shift, const float* gy, float* gx, float* ws, const BDims& b,
-                         const Dims3& d, const Fin3& fin, hipStream_t stream, const BnFuse& bn = BnFuse{}) {
-    const size_t lds = bwd_ring_bytes(b, DG, DX);
-    const dim3 grid((unsigned)(b.N * b.C * b.nbands + (FUSED ? b.C : 0))), block(kBlock);
-    switch (rounds_of(b)) {
-        case 1: hipLaunchKernelGGL((k3d_dma_backward<1, WRITE_GX, DG, DX, FUSED, QUANT, BN>), grid, block, lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
-        case 2: hipLaunchKernelGGL((k3d_dma_backward<2, WRITE_GX, DG, DX, FUSED, QUANT, BN>), grid, block, lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
-        case 3: hipLaunchKernelGGL((k3d_dma_backward<3, WRITE_GX, DG, DX, FUSED, QUANT, BN>), grid, block, lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
-        default: hipLaunchKernelGGL((k3d_dma_backward<4, WRITE_GX, DG, DX, FUSED, QUANT, BN>), grid, block, lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
+template <bool WRITE_GX, bool FUSED, bool QUANT = false, bool BN = false>
+inline void launch_bwd_r(const Cfg3& c, const float* x, const float* shift, const float* gy, float* gx, float* ws, const BDims& b,
+                         const Dims3& d, const Fin3& fin, const BnFuse& bn, hipStream_t stream) {
+    const dim3 grid(c.grid), block(kBlock);
+    switch (c.v[2]) {
+        case 1: hipLaunchKernelGGL((k3d_dma_backward<1, WRITE_GX, 1, 1, FUSED, QUANT, BN>), grid, block, c.lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
+        case 2: hipLaunchKernelGGL((k3d_dma_backward<2, WRITE_GX, 1, 1, FUSED, QUANT, BN>), grid, block, c.lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
+        case 3: hipLaunchKernelGGL((k3d_dma_backward<3, WRITE_GX, 1, 1, FUSED, QUANT, BN>), grid, block, c.lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
+        default: hipLaunchKernelGGL((k3d_dma_backward<4, WRITE_GX, 1, 1, FUSED, QUANT, BN>), grid, block, c.lds, stream, x, shift, gy, gx, ws, b, d, fin, bn); break;
     }
 }
-
-// d(shift) (+ d(x) when gx != nullptr).  One gy plane and one x plane in flight (2 / 2 measured within 1 %: the
-// memory system, not latency, bounds it).  gshift != nullptr: row-sum + K5 fused into the launch (ws holds 8-byte
-// granules [C][3][P]); gshift == nullptr: plain float partials ws[C][3][P] for a separate finalize (two-phase API).
-// Returns P (0 = not handled here).
-// quant: quantize = True (only the fused one-call form with both gradients is built for it)
-inline int launch_bwd(const float* x, const float* shift, const float* gy, float* gx, float* gshift, float* ws,
-                      const Dims3& d, int normalize, float t_factor, hipStream_t stream, bool quant = false) {
-    BDims b;
-    if (!make_bdims(b, d, true) || !aligned16(x) || !aligned16(gy) || (gx && !aligned16(gx))) return 0;
-    if (bwd_ring_bytes(b, 1, 1) > 64 * 1024) return 0;
-    Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = b.N * b.C * b.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-    if (quant) {
-        if (!(gshift && gx)) return 0;
-        launch_bwd_d<true, 1, 1, true, true>(x, shift, gy, gx, ws, b, d, fin, stream);
-    } else if (gshift) {
-        if (gx) launch_bwd_d<true, 1, 1, true>(x, shift, gy, gx, ws, b, d, fin, stream);
-        else launch_bwd_d<false, 1, 1, true>(x, shift, gy, gx, ws, b, d, fin, stream);
+// v = WRITE_GX, FUSED (row-sum + K5 inside the launch, ws = granule pairs [C][3 or 5][P]; else plain float partials
+// ws[C][3][P] for a separate finalize), ROUNDS, QUANT (quantize = True: built for the fused form with both gradients), BN
+// (training fusion: x = z, bn2's input; gx <- masked d(z); + bn2's backward constants; fused, with d(x))
+inline void launch_bwd(const Cfg3& c, const BDims& b, const Dims3& d, const float* x, const float* shift, const float* gy, float* gx,
+                       float* ws, const Fin3& fin, const BnFuse& bn, hipStream_t stream) {
+    const bool gxw = c.v[0], fused = c.v[1], quant = c.v[3];
+    if (c.v[4]) {
+        if (quant) launch_bwd_r<true, true, true, true>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
+        else launch_bwd_r<true, true, false, true>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
+    } else if (quant) launch_bwd_r<true, true, true>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
+    else if (fused) {
+        if (gxw) launch_bwd_r<true, true>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
+        else launch_bwd_r<false, true>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
     } else {
-        if (gx) launch_bwd_d<true, 1, 1, false>(x, shift, gy, gx, ws, b, d, fin, stream);
-        else launch_bwd_d<false, 1, 1, false>(x, shift, gy, gx, ws, b, d, fin, stream);
+        if (gxw) launch_bwd_r<true, false>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
+        else launch_bwd_r<false, false>(c, x, shift, gy, gx, ws, b, d, fin, bn, stream);
     }
-    return b.N * b.nbands;
-}
-
-// training fusion: x = z (bn2's input), gx <- masked d(z-activation), + bn2's backward constants.  ws: granule pairs
-// [C][5][P].  false = shape not handled here.
-inline bool launch_bwd_bn(const float* z, const float* shift, const float* gy, float* gx, float* gshift, float* ws,
-                          const Dims3& d, int normalize, float t_factor, int quantize, const BnFuse& bn, hipStream_t stream) {
-    BDims b;
-    if (!make_bdims(b, d, true) || !aligned16(z) || !aligned16(gy) || !aligned16(gx) || !aligned16(bn.abmi)) return false;
-    if (bwd_ring_bytes(b, 1, 1) > 64 * 1024) return false;
-    Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = b.N * b.C * b.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-    if (quantize) launch_bwd_d<true, 1, 1, true, true, true>(z, shift, gy, gx, ws, b, d, fin, stream, bn);
-    else launch_bwd_d<true, 1, 1, true, false, true>(z, shift, gy, gx, ws, b, d, fin, stream, bn);
-    return true;
-}
-inline int bwd_bn_partials(const Dims3& d) {
-    BDims b;
-    return make_bdims(b, d, true) ? b.N * b.nbands : 0;
 }
 
 }  // namespace dma3d

@@ -25,6 +25,15 @@ struct Dims3 {
     int sT, sH, sW, pT, pH, pW;
     int E, logE;            // threads per plane (power of two, 64..256) and its log2
 };
+// the two stride / padding classes the streaming kernels are written for
+inline bool pad0(const Dims3& d) { return d.pT == 0 && d.pH == 0 && d.pW == 0; }
+inline bool s1p0(const Dims3& d) { return d.sT == 1 && d.sH == 1 && d.sW == 1 && pad0(d); }
+inline bool s122p0(const Dims3& d) { return d.sT == 1 && d.sH == 2 && d.sW == 2 && pad0(d); }
+
+// What a planned launch (rk3d_plan.hpp) hands its family's launcher, which runs exactly that and decides nothing: the
+// variant the launcher switches on, the grid and the dynamic LDS bytes.  v[0], v[1] are NEGATE, BN of a forward /
+// d(x)-only kernel and WRITE_GX, FUSED of a backward kernel; v[2..] are the family's own (ROUNDS, SP, HALO, ...).
+struct Cfg3 { int v[5]; unsigned grid; size_t lds; };
 
 // floor/remainder of one shift component exactly as rubiks3d_kernels.cu:65-74 does it:
 // floorf() in fp32 whatever T is, remainder in T.

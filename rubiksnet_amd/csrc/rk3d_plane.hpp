@@ -20,7 +20,7 @@
 //
 // Maths, tap slots, LDS-DMA feed and the bit-exact expression trees are those of rk3d_dma.hpp / rk_dma.hpp.
 #pragma once
-#include "rk_dma.hpp"
+#include "rk3d_dma.hpp"
 
 namespace rk {
 namespace plane3d {
@@ -163,16 +163,17 @@ __global__ __launch_bounds__(kBlock) void k3d_plane_interp(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side.
+// Host side: geometry for plan3d (rk3d_plan.hpp; it has checked stride 1 / pad 0, W % 4 == 0, W >= 4, alignment and the
+// switches) and the launcher, which runs the configuration it is given.
 // Geometry: SP = 4 on half-size bands for planes up to 64 wide (56x56: two 28-row bands, 5 slots = 32.5 KB),
 // SP = 2 on the default bands for wider ones (112x112: four 28-row bands, 3 slots = 39 KB); see the header.
-inline bool make_pdims(PDims& p, int& SP, const Dims3& d) {
-    const bool s1p0 = d.sT == 1 && d.sH == 1 && d.sW == 1 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || d.W % 4 != 0 || d.W < 4 || !streaming_kernels_on()) return false;
+inline size_t slots_bytes(const BDims& b, int nslots) { return (size_t)nslots * ((b.BH + 1) * b.W4 + 1) * 16; }
+// false = not for these kernels (rk3d_dma.hpp takes it)
+inline bool geometry(PDims& p, Cfg3& c, const Dims3& d) {
     BDims& b = p.b;
-    b.N = d.N; b.T = d.T; b.C = d.C; b.H = d.H; b.W = d.W; b.W4 = d.W / 4;
+    b = dma3d::band_dims(d);
     if (!choose_bands(b)) return false;
-    SP = 2;
+    int SP = 2;
     if (b.W4 <= 16 && d.T >= 4 && b.H % (2 * b.nbands) == 0) {
         BDims h = b;
         h.nbands = 2 * b.nbands; h.BH = b.H / h.nbands;
@@ -182,44 +183,32 @@ inline bool make_pdims(PDims& p, int& SP, const Dims3& d) {
     p.G = (d.T + SP - 1) / SP;
     p.R = d.C * b.nbands;
     p.R8 = (p.R + 7) / 8 * 8;
-    return (long long)d.N * p.G * p.R8 <= 0x7fffffffLL;
+    if ((long long)d.N * p.G * p.R8 > 0x7fffffffLL) return false;
+    if (slots_bytes(b, SP + 1) > 40 * 1024) return false;            // >= 4 workgroups per CU
+    c.v[2] = rounds_of(b); c.v[3] = SP;
+    c.grid = (unsigned)(b.N * p.G * p.R8);
+    c.lds = slots_bytes(b, SP + 1);
+    return true;
 }
-inline size_t slots_bytes(const BDims& b, int nslots) { return (size_t)nslots * ((b.BH + 1) * b.W4 + 1) * 16; }
 
-template <bool NEGATE, int SP, bool BN = false>
-inline void launch_interp_sp(const float* src, const float* shift, float* dst, const PDims& p, hipStream_t stream,
-                             const float4* abmi = nullptr) {
-    const size_t lds = slots_bytes(p.b, SP + 1);
-    const dim3 grid((unsigned)(p.b.N * p.G * p.R8)), block(kBlock);
-    switch (rounds_of(p.b)) {
-        case 1: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 1, SP, BN>), grid, block, lds, stream, src, shift, dst, p, abmi); break;
-        case 2: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 2, SP, BN>), grid, block, lds, stream, src, shift, dst, p, abmi); break;
-        case 3: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 3, SP, BN>), grid, block, lds, stream, src, shift, dst, p, abmi); break;
-        default: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 4, SP, BN>), grid, block, lds, stream, src, shift, dst, p, abmi); break;
+template <bool NEGATE, int SP, bool BN>
+inline void launch_r(const Cfg3& c, const PDims& p, const float* src, const float* shift, float* dst, const float4* abmi,
+                     hipStream_t stream) {
+    const dim3 grid(c.grid), block(kBlock);
+    switch (c.v[2]) {
+        case 1: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 1, SP, BN>), grid, block, c.lds, stream, src, shift, dst, p, abmi); break;
+        case 2: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 2, SP, BN>), grid, block, c.lds, stream, src, shift, dst, p, abmi); break;
+        case 3: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 3, SP, BN>), grid, block, c.lds, stream, src, shift, dst, p, abmi); break;
+        default: hipLaunchKernelGGL((k3d_plane_interp<NEGATE, 4, SP, BN>), grid, block, c.lds, stream, src, shift, dst, p, abmi); break;
     }
 }
-
-// forward / d(x)-only; false = not handled here (rk3d_dma.hpp takes it)
-template <bool NEGATE>
-inline bool launch_interp(const float* src, const float* shift, float* dst, const Dims3& d, hipStream_t stream) {
-    PDims p;
-    int SP;
-    if (!make_pdims(p, SP, d) || !aligned16(src) || !aligned16(dst)) return false;
-    if (slots_bytes(p.b, SP + 1) > 40 * 1024) return false;          // >= 4 workgroups per CU
-    if (SP == 4) launch_interp_sp<NEGATE, 4>(src, shift, dst, p, stream);
-    else launch_interp_sp<NEGATE, 2>(src, shift, dst, p, stream);
-    return true;
-}
-// forward of relu(bn(z)) (train_block.py): abmi [C] = (a, b, mean, invstd)
-inline bool launch_forward_bn(const float* z, const float* shift, float* y, const float4* abmi, const Dims3& d,
-                              hipStream_t stream) {
-    PDims p;
-    int SP;
-    if (!make_pdims(p, SP, d) || !aligned16(z) || !aligned16(y) || !aligned16(abmi)) return false;
-    if (slots_bytes(p.b, SP + 1) > 40 * 1024) return false;
-    if (SP == 4) launch_interp_sp<false, 4, true>(z, shift, y, p, stream, abmi);
-    else launch_interp_sp<false, 2, true>(z, shift, y, p, stream, abmi);
-    return true;
+// v = NEGATE, BN (forward of relu(bn(z)), train_block.py: abmi [C] = (a, b, mean, invstd)), ROUNDS, SP
+inline void launch(const Cfg3& c, const PDims& p, const float* src, const float* shift, float* dst, const float4* abmi,
+                   hipStream_t stream) {
+    const bool sp4 = c.v[3] == 4;
+    if (c.v[1]) { if (sp4) launch_r<false, 4, true>(c, p, src, shift, dst, abmi, stream); else launch_r<false, 2, true>(c, p, src, shift, dst, abmi, stream); }
+    else if (c.v[0]) { if (sp4) launch_r<true, 4, false>(c, p, src, shift, dst, abmi, stream); else launch_r<true, 2, false>(c, p, src, shift, dst, abmi, stream); }
+    else { if (sp4) launch_r<false, 4, false>(c, p, src, shift, dst, abmi, stream); else launch_r<false, 2, false>(c, p, src, shift, dst, abmi, stream); }
 }
 
 }  // namespace plane3d

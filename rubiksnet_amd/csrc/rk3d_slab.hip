@@ -55,12 +55,6 @@ using namespace dma;
 constexpr int kMaxT = 8;          // planes resident in LDS
 constexpr int kMinHW = 16;        // (smaller planes: the column kernels)
 
-struct SDims {
-    int N, T, C, H, W, HW;
-    int slab;                     // C * HW: elements of one (n, t)
-    int nchunks;                  // ceil(slab / (256 M))
-};
-
 // M elements per lane; HALO 16-byte cells each side of a wave's piece
 template <int M, int HALO> struct Geo {
     static constexpr int kOwn = kWave * M / 4;             // 16-byte cells a wave owns per plane
@@ -565,11 +559,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) voi
 // ONE gy tap (rk3d_column.hpp, SINGLE: the tree collapses exactly to wj (v wk)), and the taps of 256 consecutive input
 // elements lie in a short run of the gy slab -- (h/2 - 1) .. (h/2 + 1) rows around them, <= 58 cells of 16 bytes -- that ONE
 // DMA instruction per plane brings into the wave's slot.  All T planes up front, counted waits, no barrier in the walk.
-struct S2Dims {
-    int N, T, C, H, W, HW, Wo, HWo;
-    int slab_in, slab_out;        // C * HW, C * HWo
-    int nchunks;                  // ceil(slab_in / 1024)
-};
 struct ElemS2 {
     unsigned rel;                 // LDS byte address (slot 0) of the element's one gy tap, or of the zero cell
     float wj, wk, sj, sk, rT;
@@ -1005,27 +994,7 @@ __global__ __launch_bounds__(kBlock) void k3d_slab_s2_forward(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side.
-// 14x14 planes: the forward / d(x)-only kernels here are level with the tile kernels at C = 216 and 10 % faster at C = 288
-// (22.0 vs 24.7 us), the fused backward is level (29.2 vs 29.1 us) and rk3d_tile.hpp has the BatchNorm-fused variants, so by
-// default only the forward comes here.  RK_SLAB14 = 1: both, 0: neither.
-static int slab14_mode() {
-    static const int v = [] { const char* e = getenv("RK_SLAB14"); return e ? (e[0] == '1' ? 2 : 0) : 1; }();
-    return v;
-}
-bool slab14_on(bool backward) { return slab14_mode() >= (backward ? 2 : 1); }
-static bool make_sdims(SDims& s, const Dims3& d, int M) {
-    const bool s1p0 = d.sT == 1 && d.sH == 1 && d.sW == 1 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || !streaming_kernels_on()) return false;
-    if (d.T > kMaxT || d.W > 15 || d.H * d.W > 256 || d.H * d.W < kMinHW) return false;
-    const long long slab = (long long)d.C * d.H * d.W;
-    if (slab % 4 != 0 || slab > 0x1fffffff) return false;
-    s.N = d.N; s.T = d.T; s.C = d.C; s.H = d.H; s.W = d.W; s.HW = d.H * d.W;
-    s.slab = (int)slab;
-    s.nchunks = (int)((slab + kBlock * M - 1) / (kBlock * M));
-    return true;
-}
-static int halo_of(const SDims& s) { return s.W + 1 <= 8 ? 2 : 4; }
+// Host side: geometry for plan3d (rk3d_plan.hpp) and launchers, which run the configuration they are given.
 template <int M, int HL, int RG> constexpr size_t lds_of() { return (size_t)(kBlock / kWave) * RG * Geo<M, HL>::kStride; }
 // planes a wave keeps in flight: 3 in the forward (16.6 / 18.2 / 21.8 us at 7x7x576 / 14x14x216 / 14x14x288 against 16.5 /
 // 18.4 / 23.3 with all 8), all 8 in the backward (95 VGPRs, 5 waves per SIMD).  The backward with a ring of 3 needed 111 VGPRs
@@ -1034,92 +1003,70 @@ template <int M, int HL, int RG> constexpr size_t lds_of() { return (size_t)(kBl
 // reachable through the RK_SLAB_RG tuning switch, is gone together with the switch.
 constexpr int kRingFwd = 3, kRingBwd = kMaxT;
 
-bool launch_interp(bool negate, const float* src, const float* shift, float* dst, const Dims3& d, hipStream_t stream) {
-    SDims s;
-    if (!make_sdims(s, d, 4) || !aligned16(src) || !aligned16(dst)) return false;
-    const unsigned grid = (unsigned)((long long)s.N * s.nchunks);
-#define RK_SLAB_FWD(NG, HL, RG) hipLaunchKernelGGL((k3d_slab_interp<NG, HL, RG>), dim3(grid), dim3(kBlock), \
-                                                   (lds_of<4, HL, RG>()), stream, src, shift, dst, s, d)
-#define RK_SLAB_FWD_R(NG, HL) RK_SLAB_FWD(NG, HL, kRingFwd)
-    if (halo_of(s) == 2) { if (negate) RK_SLAB_FWD_R(true, 2); else RK_SLAB_FWD_R(false, 2); }
-    else { if (negate) RK_SLAB_FWD_R(true, 4); else RK_SLAB_FWD_R(false, 4); }
-#undef RK_SLAB_FWD_R
-#undef RK_SLAB_FWD
+bool geometry(SDims& s, Cfg3& c, const Dims3& d, bool backward) {
+    if (d.T > kMaxT || d.W > 15 || d.H * d.W > 256 || d.H * d.W < kMinHW) return false;
+    const long long slab = (long long)d.C * d.H * d.W;
+    if (slab % 4 != 0 || slab > 0x1fffffff) return false;
+    const int M = backward ? 2 : 4, halo = d.W + 1 <= 8 ? 2 : 4;
+    s.N = d.N; s.T = d.T; s.C = d.C; s.H = d.H; s.W = d.W; s.HW = d.H * d.W;
+    s.slab = (int)slab;
+    s.nchunks = (int)((slab + kBlock * M - 1) / (kBlock * M));
+    c.v[2] = halo;
+    c.grid = (unsigned)((long long)s.N * s.nchunks);
+    if (backward) c.lds = (halo == 2 ? lds_of<2, 2, kRingBwd>() : lds_of<2, 4, kRingBwd>()) + 4 * kBlock * 2 * 4;
+    else c.lds = halo == 2 ? lds_of<4, 2, kRingFwd>() : lds_of<4, 4, kRingFwd>();
     return true;
 }
 
-int launch_bwd(const float* x, const float* shift, const float* gy, float* gx, float* gshift, float* ws, const Dims3& d,
-               int normalize, float t_factor, hipStream_t stream) {
-    SDims s;
-    if (!make_sdims(s, d, 2) || !aligned16(x) || !aligned16(gy) || (gx && !aligned16(gx))) return 0;
-    const unsigned producers = (unsigned)((long long)s.N * s.nchunks);
-    dma3d::Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = (int)producers;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-#define RK_SLAB_BWD(GX, FU, HL, RG) hipLaunchKernelGGL((k3d_slab_backward<GX, FU, HL, RG>), dim3(producers + (FU ? d.C : 0)), dim3(kBlock), \
-                                                       (lds_of<2, HL, RG>() + 4 * kBlock * 2 * 4), stream, x, shift, gy, gx, ws, s, d, fin)
-#define RK_SLAB_BWD_R(GX, FU, HL) RK_SLAB_BWD(GX, FU, HL, kRingBwd)
-#define RK_SLAB_BWD_H(GX, FU) do { if (halo_of(s) == 2) RK_SLAB_BWD_R(GX, FU, 2); else RK_SLAB_BWD_R(GX, FU, 4); } while (0)
-    if (gshift) { if (gx) RK_SLAB_BWD_H(true, true); else RK_SLAB_BWD_H(false, true); }
-    else { if (gx) RK_SLAB_BWD_H(true, false); else RK_SLAB_BWD_H(false, false); }
-#undef RK_SLAB_BWD_H
-#undef RK_SLAB_BWD_R
-#undef RK_SLAB_BWD
-    return 2 * d.N;
+void launch_interp(const Cfg3& c, const SDims& s, const Dims3& d, const float* src, const float* shift, float* dst, hipStream_t stream) {
+#define RK_SLAB_FWD(NG, HL) hipLaunchKernelGGL((k3d_slab_interp<NG, HL, kRingFwd>), dim3(c.grid), dim3(kBlock), c.lds, stream, src, shift, dst, s, d)
+    if (c.v[2] == 2) { if (c.v[0]) RK_SLAB_FWD(true, 2); else RK_SLAB_FWD(false, 2); }
+    else { if (c.v[0]) RK_SLAB_FWD(true, 4); else RK_SLAB_FWD(false, 4); }
+#undef RK_SLAB_FWD
 }
 
+void launch_bwd(const Cfg3& c, const SDims& s, const Dims3& d, const float* x, const float* shift, const float* gy, float* gx, float* ws,
+                const dma3d::Fin3& fin, hipStream_t stream) {
+#define RK_SLAB_BWD(GX, FU, HL) hipLaunchKernelGGL((k3d_slab_backward<GX, FU, HL, kRingBwd>), dim3(c.grid), dim3(kBlock), c.lds, stream, \
+                                                   x, shift, gy, gx, ws, s, d, fin)
+#define RK_SLAB_BWD_H(GX, FU) do { if (c.v[2] == 2) RK_SLAB_BWD(GX, FU, 2); else RK_SLAB_BWD(GX, FU, 4); } while (0)
+    if (c.v[1]) { if (c.v[0]) RK_SLAB_BWD_H(true, true); else RK_SLAB_BWD_H(false, true); }
+    else { if (c.v[0]) RK_SLAB_BWD_H(true, false); else RK_SLAB_BWD_H(false, false); }
+#undef RK_SLAB_BWD_H
+#undef RK_SLAB_BWD
+}
 
-// forward of the same layers; false = not handled here
-bool launch_fwd_s2(const float* x, const float* shift, float* y, const Dims3& d, hipStream_t stream) {
-    const bool s122 = d.sT == 1 && d.sH == 2 && d.sW == 2 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!s122 || !streaming_kernels_on()) return false;
+// (the forward takes C * Ho * Wo % 2 == 0, the backward needs % 4)
+bool geometry_s2(S2Dims& s, Cfg3& c, const Dims3& d, bool backward) {
     if (d.T > kMaxT || (d.H & 1) || (d.W & 1) || d.W > 56 || d.W < 4 || d.H < 2) return false;
     const long long slab_in = (long long)d.C * d.H * d.W, slab_out = (long long)d.C * d.Ho * d.Wo;
-    if (slab_in % 4 != 0 || slab_out % 2 != 0 || slab_in > 0x1fffffff) return false;
-    if (!aligned16(x) || !aligned16(y)) return false;
-    // the piece of a wave: 4 x 128 floats of windows + a row and a column each side, in 16-byte cells
-    if ((4 * kWave * 2 + 2 * d.W + 2 + 3) / 4 + 2 > kF2Cells) return false;
-    S2Dims s;
+    if (slab_in % 4 != 0 || slab_out % (backward ? 4 : 2) != 0 || slab_in > 0x1fffffff) return false;
+    // forward, the piece of a wave: 4 x 128 floats of windows + a row and a column each side, in 16-byte cells
+    if (!backward && (4 * kWave * 2 + 2 * d.W + 2 + 3) / 4 + 2 > kF2Cells) return false;
     s.N = d.N; s.T = d.T; s.C = d.C; s.H = d.H; s.W = d.W; s.HW = d.H * d.W; s.Wo = d.Wo; s.HWo = d.Ho * d.Wo;
     s.slab_in = (int)slab_in; s.slab_out = (int)slab_out;
-    s.nchunks = 0;
-    const unsigned grid = (unsigned)((long long)s.N * ((slab_out + kF2Chunk - 1) / kF2Chunk));
-    hipLaunchKernelGGL(k3d_slab_s2_forward, dim3(grid), dim3(kBlock), (size_t)(kBlock / kWave) * kF2RG * kF2Stride, stream, x, shift, y, s, d);
+    s.nchunks = backward ? (int)((slab_in + kS2Chunk - 1) / kS2Chunk) : 0;
+    if (backward) {
+        c.grid = (unsigned)((long long)s.N * s.nchunks);
+        c.lds = (size_t)(kBlock / kWave) * kMaxT * kS2Stride + 4 * kS2Chunk * 4;
+    } else {
+        c.grid = (unsigned)((long long)s.N * ((slab_out + kF2Chunk - 1) / kF2Chunk));
+        c.lds = (size_t)(kBlock / kWave) * kF2RG * kF2Stride;
+    }
     return true;
 }
 
-// stride (1,2,2) backward of the small strided layers (28 -> 14, 14 -> 7); returns P (0 = not handled here)
-int launch_bwd_s2(const float* x, const float* shift, const float* gy, float* gx, float* gshift, float* ws, const Dims3& d,
-                  int normalize, float t_factor, hipStream_t stream) {
-    const bool s122 = d.sT == 1 && d.sH == 2 && d.sW == 2 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!s122 || !streaming_kernels_on()) return 0;
-    if (d.T > kMaxT || (d.H & 1) || (d.W & 1) || d.W > 56 || d.W < 4 || d.H < 2) return 0;
-    const long long slab_in = (long long)d.C * d.H * d.W, slab_out = (long long)d.C * d.Ho * d.Wo;
-    if (slab_in % 4 != 0 || slab_out % 4 != 0 || slab_in > 0x1fffffff) return 0;
-    if (!aligned16(x) || !aligned16(gy) || (gx && !aligned16(gx))) return 0;
-    S2Dims s;
-    s.N = d.N; s.T = d.T; s.C = d.C; s.H = d.H; s.W = d.W; s.HW = d.H * d.W; s.Wo = d.Wo; s.HWo = d.Ho * d.Wo;
-    s.slab_in = (int)slab_in; s.slab_out = (int)slab_out;
-    s.nchunks = (int)((slab_in + kS2Chunk - 1) / kS2Chunk);
-    const unsigned producers = (unsigned)((long long)s.N * s.nchunks);
-    dma3d::Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = (int)producers;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-    const size_t lds = (size_t)(kBlock / kWave) * kMaxT * kS2Stride + 4 * kS2Chunk * 4;
-#define RK_SLAB_S2(GX, FU) hipLaunchKernelGGL((k3d_slab_s2_backward<GX, FU>), dim3(producers + (FU ? d.C : 0)), dim3(kBlock), lds, \
-                                              stream, x, shift, gy, gx, ws, s, d, fin)
-    if (gshift) { if (gx) RK_SLAB_S2(true, true); else RK_SLAB_S2(false, true); }
-    else { if (gx) RK_SLAB_S2(true, false); else RK_SLAB_S2(false, false); }
+void launch_fwd_s2(const Cfg3& c, const S2Dims& s, const Dims3& d, const float* x, const float* shift, float* y, hipStream_t stream) {
+    hipLaunchKernelGGL(k3d_slab_s2_forward, dim3(c.grid), dim3(kBlock), c.lds, stream, x, shift, y, s, d);
+}
+
+void launch_bwd_s2(const Cfg3& c, const S2Dims& s, const Dims3& d, const float* x, const float* shift, const float* gy, float* gx,
+                   float* ws, const dma3d::Fin3& fin, hipStream_t stream) {
+#define RK_SLAB_S2(GX, FU) hipLaunchKernelGGL((k3d_slab_s2_backward<GX, FU>), dim3(c.grid), dim3(kBlock), c.lds, stream, x, shift, gy, gx, \
+                                              ws, s, d, fin)
+    if (c.v[1]) { if (c.v[0]) RK_SLAB_S2(true, true); else RK_SLAB_S2(false, true); }
+    else { if (c.v[0]) RK_SLAB_S2(true, false); else RK_SLAB_S2(false, false); }
 #undef RK_SLAB_S2
-    return 2 * d.N;
 }
 
 }  // namespace slab3d

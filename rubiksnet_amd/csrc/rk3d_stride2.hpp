@@ -497,88 +497,43 @@ __global__ __launch_bounds__(kBlock) void k3d_s2_backward(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side.  false = shape not handled here.
-inline bool make_sdims(SDims& s, const Dims3& d) {
-    const bool ok = d.sT == 1 && d.sH == 2 && d.sW == 2 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!ok || d.W % 4 != 0 || d.Wo % 4 != 0 || d.H % 2 != 0 || d.W % 2 != 0 || !streaming_kernels_on()) return false;
+// Host side: geometry for plan3d (rk3d_plan.hpp; it has checked stride (1,2,2) / pad 0, alignment and the switches) and
+// launchers, which run the configuration they are given.
+inline size_t ring_bytes(const SDims& s, int slots) { return (size_t)slots * (2 * s.BHo * s.W4 + 1) * 16; }
+inline size_t bwd_lds_bytes(const SDims& s) { return ((size_t)3 * (2 * s.BHo * s.W4 + 1) + kBlock + 1) * 16; }
+// false = not for these kernels.  c.grid: the producers (a FUSED backward launch adds C finalizer blocks); P = s.N * s.nbands
+inline bool geometry(SDims& s, Cfg3& c, const Dims3& d, bool backward) {
+    if (d.W % 4 != 0 || d.Wo % 4 != 0 || d.H % 2 != 0 || d.W % 2 != 0) return false;
     s.N = d.N; s.T = d.T; s.C = d.C; s.H = d.H; s.W = d.W; s.W4 = d.W / 4;
     s.Ho = d.Ho; s.Wo = d.Wo; s.Wo4 = d.Wo / 4;
-    for (int nb = 1; nb <= s.Ho; ++nb) {                           // fewest bands with <= 1024 slot cells, <= 256 outputs
-        if (s.Ho % nb) continue;
+    s.nbands = 0;
+    for (int nb = 1; nb <= s.Ho && !s.nbands; ++nb) {              // fewest bands with <= 1024 slot cells, <= 256 outputs
         const int bh = s.Ho / nb;
-        if (2 * bh * s.W4 > 4 * kBlock || bh * s.Wo4 > kBlock) continue;
+        if (s.Ho % nb || 2 * bh * s.W4 > 4 * kBlock || bh * s.Wo4 > kBlock) continue;
         s.BHo = bh; s.nbands = nb;
-        return true;
     }
-    return false;
-}
-inline size_t ring_bytes(const SDims& s, int slots) { return (size_t)slots * (2 * s.BHo * s.W4 + 1) * 16; }
-
-inline bool launch_forward(const float* x, const float* shift, float* y, const Dims3& d, hipStream_t stream) {
-    constexpr int D = 2;
-    SDims s;
-    if (!make_sdims(s, d) || !aligned16(x) || !aligned16(y)) return false;
-    const size_t lds = ring_bytes(s, D + 1);
-    if (lds > 64 * 1024) return false;
-    const dim3 grid((unsigned)(s.N * s.C * s.nbands)), block(kBlock);
-    hipLaunchKernelGGL((k3d_s2_forward<4, D>), grid, block, lds, stream, x, shift, y, s);
+    const size_t lds = backward ? bwd_lds_bytes(s) : ring_bytes(s, 3);      // forward: 2 planes in flight
+    if (!s.nbands || lds > 64 * 1024) return false;
+    c.grid = (unsigned)(s.N * s.C * s.nbands);
+    c.lds = lds;
     return true;
 }
-
-// training fusion (BN): forward of relu(bn(z)) and its backward; false = not handled here
-inline bool launch_forward_bn(const float* z, const float* shift, float* y, const float4* abmi, const Dims3& d,
-                              hipStream_t stream) {
-    constexpr int D = 2;
-    SDims s;
-    if (!make_sdims(s, d) || !aligned16(z) || !aligned16(y) || !aligned16(abmi)) return false;
-    const size_t lds = ring_bytes(s, D + 1);
-    if (lds > 64 * 1024) return false;
-    const dim3 grid((unsigned)(s.N * s.C * s.nbands)), block(kBlock);
-    hipLaunchKernelGGL((k3d_s2_forward<4, D, true>), grid, block, lds, stream, z, shift, y, s, abmi);
-    return true;
+// v[1] = BN (training fusion: forward of relu(bn(z)))
+inline void launch_forward(const Cfg3& c, const SDims& s, const float* x, const float* shift, float* y, const float4* abmi,
+                           hipStream_t stream) {
+    if (c.v[1]) hipLaunchKernelGGL((k3d_s2_forward<4, 2, true>), dim3(c.grid), dim3(kBlock), c.lds, stream, x, shift, y, s, abmi);
+    else hipLaunchKernelGGL((k3d_s2_forward<4, 2>), dim3(c.grid), dim3(kBlock), c.lds, stream, x, shift, y, s);
 }
-inline size_t bwd_lds_bytes(const SDims& s);
-inline bool launch_backward_bn(const float* z, const float* shift, const float* gy, float* gx, float* gshift, float* ws,
-                               const Dims3& d, int normalize, float t_factor, const dma3d::BnFuse& bn, hipStream_t stream) {
-    SDims s;
-    if (!make_sdims(s, d) || !aligned16(z) || !aligned16(gy) || !aligned16(gx) || !aligned16(bn.abmi)) return false;
-    const size_t lds = bwd_lds_bytes(s);
-    if (lds > 64 * 1024) return false;
-    dma3d::Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = s.N * s.C * s.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-    hipLaunchKernelGGL((k3d_s2_backward<4, true, true, true>), dim3((unsigned)(fin.f.producers + s.C)), dim3(kBlock), lds, stream,
-                       z, shift, gy, gx, ws, s, d, fin, bn);
-    return true;
-}
-
-// d(shift) (+ d(x) when gx != nullptr); gshift != nullptr: row-sum + K5 inside the launch (ws = 8-byte granules
-// [C][3][P]), else plain partials ws[C][3][P] for the two-phase ABI.  Returns P (0 = not handled here).
-inline size_t bwd_lds_bytes(const SDims& s) { return ((size_t)3 * (2 * s.BHo * s.W4 + 1) + kBlock + 1) * 16; }
-inline int launch_backward(const float* x, const float* shift, const float* gy, float* gx, float* gshift, float* ws,
-                           const Dims3& d, int normalize, float t_factor, hipStream_t stream) {
-    SDims s;
-    if (!make_sdims(s, d) || !aligned16(x) || !aligned16(gy) || (gx && !aligned16(gx))) return 0;
-    const size_t lds = bwd_lds_bytes(s);
-    if (lds > 64 * 1024) return 0;
-    dma3d::Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = s.N * s.C * s.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-    const dim3 block(kBlock);
-#define RK_S2_LAUNCH(GX, FU) hipLaunchKernelGGL((k3d_s2_backward<4, GX, FU>), dim3((unsigned)(fin.f.producers + (FU ? s.C : 0))), \
-                                                block, lds, stream, x, shift, gy, gx, ws, s, d, fin)
-    if (gshift) { if (gx) RK_S2_LAUNCH(true, true); else RK_S2_LAUNCH(false, true); }
-    else { if (gx) RK_S2_LAUNCH(true, false); else RK_S2_LAUNCH(false, false); }
+// v = WRITE_GX, FUSED (row-sum + K5 inside the launch, ws = 8-byte granules [C][3][P]; else plain partials ws[C][3][P]
+// for the two-phase ABI), BN (fused, with d(x))
+inline void launch_backward(const Cfg3& c, const SDims& s, const Dims3& d, const float* x, const float* shift, const float* gy,
+                            float* gx, float* ws, const dma3d::Fin3& fin, const dma3d::BnFuse& bn, hipStream_t stream) {
+#define RK_S2_LAUNCH(...) hipLaunchKernelGGL((k3d_s2_backward<4, __VA_ARGS__>), dim3(c.grid), dim3(kBlock), c.lds, stream, x, shift, gy, \
+                                             gx, ws, s, d, fin, bn)
+    if (c.v[2]) RK_S2_LAUNCH(true, true, true);
+    else if (c.v[1]) { if (c.v[0]) RK_S2_LAUNCH(true, true); else RK_S2_LAUNCH(false, true); }
+    else { if (c.v[0]) RK_S2_LAUNCH(true, false); else RK_S2_LAUNCH(false, false); }
 #undef RK_S2_LAUNCH
-    return s.N * s.nbands;
 }
 
 }  // namespace s2

@@ -364,75 +364,32 @@ __global__ __launch_bounds__(kBlock) void k3d_tile14_backward(const float* __res
 }  // namespace t14
 
 // ---------------------------------------------------------------------------------------------
-// Host side.
-inline bool s1p0(const Dims3& d) {
-    return d.sT == 1 && d.sH == 1 && d.sW == 1 && d.pT == 0 && d.pH == 0 && d.pW == 0 && streaming_kernels_on();
+// Host side: geometry for plan3d (rk3d_plan.hpp; it has checked stride 1 / pad 0, the 14 x 14 plane, alignment and the
+// switches) and launchers, which run the configuration they are given.
+// c.grid: the producers (a FUSED backward launch adds C finalizer blocks); P = N
+inline void geometry(Cfg3& c, const Dims3& d, bool backward) {
+    c.grid = (unsigned)(((long long)d.N * d.C + 3) / 4);
+    c.lds = 4 * (backward ? t14::kSlotsBwd : 3) * t14::kStride;
 }
-
-// forward / d(x)-only; false = not handled here
-template <bool NEGATE>
-inline bool launch_interp(const float* src, const float* shift, float* dst, const Dims3& d, hipStream_t stream) {
-    if (!s1p0(d) || !aligned16(src) || !aligned16(dst)) return false;
-    if (d.H != 14 || d.W != 14) return false;
-    TDims t{d.N, d.T, d.C};
-    const unsigned grid = (unsigned)(((long long)d.N * d.C + 3) / 4);
-    hipLaunchKernelGGL((t14::k3d_tile14_interp<NEGATE>), dim3(grid), dim3(kBlock), 4 * 3 * t14::kStride, stream, src, shift,
-                       dst, t);
-    return true;
+// v = NEGATE, BN (training fusion: forward of relu(bn(z)))
+inline void launch_interp(const Cfg3& c, const Dims3& d, const float* src, const float* shift, float* dst, const float4* abmi,
+                          hipStream_t stream) {
+    const TDims t{d.N, d.T, d.C};
+    const dim3 grid(c.grid), block(kBlock);
+    if (c.v[1]) hipLaunchKernelGGL((t14::k3d_tile14_interp<false, true>), grid, block, c.lds, stream, src, shift, dst, t, abmi);
+    else if (c.v[0]) hipLaunchKernelGGL((t14::k3d_tile14_interp<true>), grid, block, c.lds, stream, src, shift, dst, t);
+    else hipLaunchKernelGGL((t14::k3d_tile14_interp<false>), grid, block, c.lds, stream, src, shift, dst, t);
 }
-
-// training fusion (BN): forward of relu(bn(z)) and its backward; false = not handled here
-inline bool launch_forward_bn(const float* z, const float* shift, float* y, const float4* abmi, const Dims3& d,
-                              hipStream_t stream) {
-    if (!s1p0(d) || !aligned16(z) || !aligned16(y) || !aligned16(abmi)) return false;
-    if (d.H != 14 || d.W != 14) return false;
-    TDims t{d.N, d.T, d.C};
-    const unsigned grid = (unsigned)(((long long)d.N * d.C + 3) / 4);
-    hipLaunchKernelGGL((t14::k3d_tile14_interp<false, true>), dim3(grid), dim3(kBlock), 4 * 3 * t14::kStride, stream, z, shift,
-                       y, t, abmi);
-    return true;
-}
-inline bool launch_bwd_bn(const float* z, const float* shift, const float* gy, float* gx, float* gshift, float* ws,
-                          const Dims3& d, int normalize, float t_factor, const dma3d::BnFuse& bn, hipStream_t stream) {
-    if (!s1p0(d) || !aligned16(z) || !aligned16(gy) || !aligned16(gx) || !aligned16(bn.abmi)) return false;
-    if (d.H != 14 || d.W != 14) return false;
-    TDims t{d.N, d.T, d.C};
-    const unsigned producers = (unsigned)(((long long)d.N * d.C + 3) / 4);
-    const size_t lds = 4 * t14::kSlotsBwd * t14::kStride;
-    dma3d::Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = (int)producers;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-    hipLaunchKernelGGL((t14::k3d_tile14_backward<true, true, true>), dim3(producers + d.C), dim3(kBlock), lds, stream, z, shift,
-                       gy, gx, ws, t, d, fin, bn);
-    return true;
-}
-
-// d(shift) (+ d(x) when gx != nullptr); gshift != nullptr: row-sum + K5 fused into the launch (ws = granules), else
-// plain partials ws[C][3][P].  Returns P (0 = not handled here)
-inline int launch_bwd(const float* x, const float* shift, const float* gy, float* gx, float* gshift, float* ws,
-                      const Dims3& d, int normalize, float t_factor, hipStream_t stream) {
-    if (!s1p0(d) || !aligned16(x) || !aligned16(gy) || (gx && !aligned16(gx))) return 0;
-    if (d.H != 14 || d.W != 14) return 0;
-    TDims t{d.N, d.T, d.C};
-    const unsigned producers = (unsigned)(((long long)d.N * d.C + 3) / 4);
-    const size_t lds = 4 * t14::kSlotsBwd * t14::kStride;
-    dma3d::Fin3 fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = (int)producers;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    fin.t_factor = t_factor;
-#define RK_T14_BWD(GX, FU) hipLaunchKernelGGL((t14::k3d_tile14_backward<GX, FU>), dim3(producers + (FU ? d.C : 0)), \
-                                              dim3(kBlock), lds, stream, x, shift, gy, gx, ws, t, d, fin)
-    if (gshift) { if (gx) RK_T14_BWD(true, true); else RK_T14_BWD(false, true); }
-    else { if (gx) RK_T14_BWD(true, false); else RK_T14_BWD(false, false); }
+// v = WRITE_GX, FUSED (row-sum + K5 inside the launch, ws = granules; else plain partials ws[C][3][P]), BN (fused, with d(x))
+inline void launch_bwd(const Cfg3& c, const Dims3& d, const float* x, const float* shift, const float* gy, float* gx, float* ws,
+                       const dma3d::Fin3& fin, const dma3d::BnFuse& bn, hipStream_t stream) {
+    const TDims t{d.N, d.T, d.C};
+#define RK_T14_BWD(...) hipLaunchKernelGGL((t14::k3d_tile14_backward<__VA_ARGS__>), dim3(c.grid), dim3(kBlock), c.lds, stream, x, shift, \
+                                           gy, gx, ws, t, d, fin, bn)
+    if (c.v[2]) RK_T14_BWD(true, true, true);
+    else if (c.v[1]) { if (c.v[0]) RK_T14_BWD(true, true); else RK_T14_BWD(false, true); }
+    else { if (c.v[0]) RK_T14_BWD(true, false); else RK_T14_BWD(false, false); }
 #undef RK_T14_BWD
-    return d.N;
 }
 
 }  // namespace tile3d

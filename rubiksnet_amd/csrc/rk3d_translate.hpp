@@ -51,18 +51,19 @@ __global__ __launch_bounds__(kBlock) void k3d_translate(const float* __restrict_
     }
 }
 
-// false = not handled here (stride / padding / W % 4 / alignment)
-template <bool NEGATE>
-inline bool launch(const float* src, const float* shift, float* dst, Dims3 d, hipStream_t stream) {
-    const bool s1p0 = d.sT == 1 && d.sH == 1 && d.sW == 1 && d.pT == 0 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || d.W % 4 != 0 || !dma::aligned16(dst) || !streaming_kernels_on()) return false;
+// for plan3d (rk3d_plan.hpp; it has checked stride 1 / pad 0, W % 4 == 0, the alignment of dst and the switches): E, grid
+inline void geometry(Dims3& d, Cfg3& c) {
     d.E = pow2_at_least(d.H * d.W / 4, kWave, kBlock);
     d.logE = (d.E == 64) ? 6 : (d.E == 128 ? 7 : 8);
     const long long planes = (long long)d.N * d.T * d.C;
     const int per_block = kBlock / d.E;
-    hipLaunchKernelGGL((k3d_translate<NEGATE>), dim3((unsigned)((planes + per_block - 1) / per_block)), dim3(kBlock), 0,
-                       stream, src, shift, dst, d);
-    return true;
+    c.grid = (unsigned)((planes + per_block - 1) / per_block);
+    c.lds = 0;
+}
+// v = NEGATE
+inline void launch(const Cfg3& c, const Dims3& d, const float* src, const float* shift, float* dst, hipStream_t stream) {
+    if (c.v[0]) hipLaunchKernelGGL((k3d_translate<true>), dim3(c.grid), dim3(kBlock), 0, stream, src, shift, dst, d);
+    else hipLaunchKernelGGL((k3d_translate<false>), dim3(c.grid), dim3(kBlock), 0, stream, src, shift, dst, d);
 }
 
 }  // namespace xlate3d

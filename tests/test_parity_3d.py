@@ -5,6 +5,8 @@ Bars: forward and d(x) BIT-EXACT in fp32 and fp64 (both sides evaluate the refer
 expression tree with FP contraction off; quantize is a pure gather); d(shift) within
 1e-5 (relative to the gradient's scale) of the oracle evaluated in fp64.
 """
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -190,6 +192,40 @@ def test_two_phase_backward_equals_the_one_call_form():
         assert P.value > 0
         _native.check(L.rk3d_backward_finalize_f32(ws.data_ptr(), C, P.value, gs2.data_ptr(), 1, 0.5, st), "finalize")
         assert torch.equal(gx1, gx2) and torch.equal(gs1, gs2)
+
+
+def test_partials_count_is_the_planned_one():
+    """The one observable link between the plan (rk3d_plan.hpp, tests/test_plan3d.py) and what ran: for the smallest shape of
+    each kernel family the count rk3d_backward_partials_f32 reports equals the P planned for the same call."""
+    import ctypes
+
+    from rubiksnet_amd import _native
+
+    L = _native.lib()
+    sk = {"column": 1, "generic": 2}.get(os.environ.get("RK_SHIFT_KERNELS"), 2 if os.environ.get("RK_FORCE_GENERIC", "")[:1] == "1" else 0)
+    s14 = os.environ.get("RK_SLAB14")
+    s14 = -1 if s14 is None else int(s14[:1] == "1")
+    out = (ctypes.c_int * 30)()
+    st = torch.cuda.current_stream().cuda_stream
+    for (N, T, C, H, W), s, p in (((2, 8, 6, 56, 56), (1, 1, 1), (0, 0, 0)), ((1, 4, 5, 28, 28), (1, 1, 1), (0, 0, 0)),
+                                  ((3, 5, 6, 14, 14), (1, 1, 1), (0, 0, 0)), ((3, 8, 9, 7, 7), (1, 1, 1), (0, 0, 0)),
+                                  ((2, 3, 4, 56, 56), (1, 2, 2), (0, 0, 0)), ((1, 5, 4, 10, 12), (1, 2, 2), (0, 0, 0)),
+                                  ((1, 6, 3, 10, 11), (2, 1, 3), (1, 2, 0))):
+        torch.manual_seed(C + H)
+        x = torch.rand(N, T, C, H, W, device="cuda:0") * 2 - 1
+        shift = torch.rand(3, C, device="cuda:0") * 2 - 1
+        To, Ho, Wo = (L.rk_out_len(v, sv, pv) for v, sv, pv in zip((T, H, W), s, p))
+        gy = torch.rand(N, To, C, Ho, Wo, device="cuda:0") * 2 - 1
+        gx = torch.empty_like(x)
+        nbytes = int(L.rk3d_backward_workspace_bytes(N, T, C, H, W, *s, *p, 4))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda:0")
+        P = ctypes.c_int(0)
+        _native.check(L.rk3d_backward_partials_f32(x.data_ptr(), shift.data_ptr(), gy.data_ptr(), gx.data_ptr(), N, T, C, H, W,
+                                                   *s, *p, 0, ws.data_ptr(), nbytes, ctypes.byref(P), st), "partials")
+        aligned = sum(bit for bit, t in ((1, x), (2, gy), (4, gx)) if t.data_ptr() % 16 == 0) | 8
+        assert L.rk_debug_3d_plan(1, 4, N, T, C, H, W, *s, *p, 0, 1, 1, 1, aligned, sk, s14, out) == 0
+        assert P.value == out[1] > 0, ((N, T, C, H, W), s, P.value, out[1])
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("shape,stride", [((2, 8, 6, 56, 56), 1), ((2, 4, 8, 14, 14), 1), ((2, 3, 4, 56, 56), 2),
