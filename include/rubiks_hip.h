@@ -68,7 +68,7 @@ enum {
     RK_ERR_LAUNCH = -5,        /* hipGetLastError() after a launch was not hipSuccess */
     RK_ERR_NO_DEVICE = -6,     /* no usable HIP device */
     RK_ERR_UNSUPPORTED = -7    /* the fused entry point has no kernel for this configuration: nothing was launched, use
-                                  the unfused entry points (only the *_bn_* entry points return it) */
+                                  the unfused entry points (only the *_bn_* entry points and the planner's test hook return it) */
 };
 
 int rk_version(void);                 /* 1000*major + minor */
@@ -118,7 +118,7 @@ int rk_debug_pw_gemm_plan(int F, int K, int M, int P, int a_is_mk, int aligned, 
 int rk_debug_pw_wgrad_plan(int F, int K, int M, int P, int pw2);
 /* the RubiksShift3D kernel choice (rk3d_plan.hpp: plan3d::plan) with explicit switches and one alignment bit per operand, no
  * device call.  form: 0 forward, 1 backward (want_gx / want_gshift; two_phase: rk3d_backward_partials_f32), 2 rk3d_forward_bn_f32,
- * 3 rk3d_backward_bn_f32; elem_size 4 / 8; aligned (16 bytes): 1 x / z, 2 y (forward) or gy, 4 gx / dz, 8 the BatchNorm pack;
+ * 3 rk3d_backward_bn_f32; elem_size 4 / 8 / 2 (the 16-bit entry points; forms 2, 3 and two_phase: RK_ERR_UNSUPPORTED); aligned (16 bytes): 1 x / z, 2 y (forward) or gy, 4 gx / dz, 8 the BatchNorm pack;
  * shift_kernels: 0 auto, 1 column, 2 generic (RK_SHIFT_KERNELS); slab14: -1 unset, 0, 1 (RK_SLAB14).  Returns the status the
  * call would have as far as it does not depend on pointers.  out[30]: launches, P (partials per channel and sum: the workspace
  * holds [C][3 or 5][P]), whether a separate finalize launch follows, then per launch (3 x 9): family (the enum of
@@ -142,7 +142,7 @@ int rk3d_forward_f64(const double* x, const double* shift, double* y,
                      int pad_T, int pad_H, int pad_W,
                      int quantize, rk_stream_t stream);
 
-/* Bytes of scratch rk3d_backward_* needs (elem_size = 4 or 8).  Replaces the
+/* Bytes of scratch rk3d_backward_* needs (elem_size = 4 or 8; 2: the 16-bit entry points, plain fp32 partials).  Replaces the
  * zeros[3C,Ho,Wo] + ones[Ho,Wo] allocations of rubiks.cpp:294-299.  The scratch needs NO initialisation and may be
  * reused by the next call on the same stream: the streaming fp32 kernels keep their partials there as 8-byte
  * {value, launch tag} granules and run the row-sum + K5 inside the backward launch. */
@@ -183,6 +183,47 @@ int rk3d_backward_partials_f32(const float* x, const float* shift, const float* 
                                rk_stream_t stream);
 int rk3d_backward_finalize_f32(const void* workspace, int C, int partials, float* gshift,
                                int normalize_grad, float normalize_t_factor, rk_stream_t stream);
+
+/* RubiksShift3D on 16-bit activations with the shift table and d(shift) in fp32 -- what torch.autocast hands the operator:
+ * bf16 / f16 x, y, gy and gx next to an fp32 parameter.  The shift is never rounded to the storage type; the arithmetic is
+ * the fp32 operator's, in fp32 (same expression trees, contraction off), and a result is rounded to the storage type once,
+ * on store, round-to-nearest-even.  So y and gx are, bit for bit, what the fp32 entry points give on the widened tensors,
+ * narrowed -- quantize included.  gshift is summed in fp32 per partial, then in a fixed order in fp64 per channel, as in
+ * the fp32 operator; normalize_grad / normalize_t_factor as there.  gx or gshift may be NULL to skip that half; the
+ * workspace (needed for gshift only) is the one for elem_size = 2.  Validation order and error codes as the fp32 entry
+ * points.  Stride (1,1,1) / pad 0 / quantize off configurations whose slabs of G planes are whole 16-byte chunks run on the
+ * streaming kernels when every tensor is 16-byte aligned (csrc/rk3d_16.hip); everything else runs on the per-plane kernels
+ * at 16-bit storage.  No BatchNorm-fused and no two-phase form exists for these types. */
+int rk3d_forward_bf16_sf32(const void* x, const float* shift, void* y,
+                           int N, int T, int C, int H, int W,
+                           int stride_T, int stride_H, int stride_W,
+                           int pad_T, int pad_H, int pad_W,
+                           int quantize, rk_stream_t stream);
+int rk3d_forward_f16_sf32(const void* x, const float* shift, void* y,
+                          int N, int T, int C, int H, int W,
+                          int stride_T, int stride_H, int stride_W,
+                          int pad_T, int pad_H, int pad_W,
+                          int quantize, rk_stream_t stream);
+int rk3d_backward_bf16_sf32(const void* x, const float* shift, const void* gy,
+                            void* gx, float* gshift,
+                            int N, int T, int C, int H, int W,
+                            int stride_T, int stride_H, int stride_W,
+                            int pad_T, int pad_H, int pad_W,
+                            int normalize_grad, float normalize_t_factor, int quantize,
+                            void* workspace, size_t workspace_bytes, rk_stream_t stream);
+int rk3d_backward_f16_sf32(const void* x, const float* shift, const void* gy,
+                           void* gx, float* gshift,
+                           int N, int T, int C, int H, int W,
+                           int stride_T, int stride_H, int stride_W,
+                           int pad_T, int pad_H, int pad_W,
+                           int normalize_grad, float normalize_t_factor, int quantize,
+                           void* workspace, size_t workspace_bytes, rk_stream_t stream);
+/* 1 when the streaming 16-bit kernels take the configuration (elem_size must be 2), pointer alignment aside, else 0.  A
+ * pure host predicate, no device call: the Python layer routes autocast activations to the entry points above where it
+ * says 1 and keeps the fp32 operator between two casts elsewhere. */
+int rk3d_sf32_streams(int N, int T, int C, int H, int W,
+                      int stride_T, int stride_H, int stride_W,
+                      int pad_T, int pad_H, int pad_W, int quantize, int elem_size);
 
 /* ------------------------------------------------------------------------- 2D
  * Replaces rubiks2d_forward (cuda_src/rubiks.cpp:44-67) + rubiks2d_forward_cuda

@@ -40,6 +40,12 @@ SIGNATURES = {
     "rk3d_backward_workspace_bytes": (_sz, _DIMS3 + [_i]),
     "rk3d_backward_f32": (_i, [_p] * 5 + _DIMS3 + [_i, ctypes.c_float, _i, _p, _sz, _p]),
     "rk3d_backward_f64": (_i, [_p] * 5 + _DIMS3 + [_i, ctypes.c_double, _i, _p, _sz, _p]),
+    # 16-bit activations, fp32 shift table / d(shift)
+    "rk3d_forward_bf16_sf32": (_i, [_p, _p, _p] + _DIMS3 + [_i, _p]),
+    "rk3d_forward_f16_sf32": (_i, [_p, _p, _p] + _DIMS3 + [_i, _p]),
+    "rk3d_backward_bf16_sf32": (_i, [_p] * 5 + _DIMS3 + [_i, ctypes.c_float, _i, _p, _sz, _p]),
+    "rk3d_backward_f16_sf32": (_i, [_p] * 5 + _DIMS3 + [_i, ctypes.c_float, _i, _p, _sz, _p]),
+    "rk3d_sf32_streams": (_i, _DIMS3 + [_i, _i]),
     "rk3d_backward_partials_f32": (_i, [_p] * 4 + _DIMS3 + [_i, _p, _sz, ctypes.POINTER(ctypes.c_int), _p]),
     "rk3d_backward_finalize_f32": (_i, [_p, _i, _i, _p, _i, ctypes.c_float, _p]),
     "rk2d_backward_workspace_bytes": (_sz, _DIMS2 + [_i]),

@@ -16,6 +16,9 @@
 
     RK_PRESOFT     1 | 0          train step: the [C, 3] tap softmax of every AttentionShift layer in one launch each way
                                   (attention_shift.presoftened) / one launch per layer and direction
+    RK_SHIFT3D_16  1 | 0          bf16 / f16 activations next to an fp32 shift table (autocast): RubiksShift3D runs natively on
+                                  the 16-bit tensors (rk3d_*_sf32) wherever the streaming 16-bit kernels take the layer
+                                  (rk3d_sf32_streams) / everywhere the fp32 operator between two casts
 
 Everything else that used to be tunable from the environment (tile shapes, channel limits, prefetch depths)
 is a constant next to the code it tunes.  The native library reads its own switches once per process
@@ -41,6 +44,7 @@ class Switches:
     prepack: bool = True
     bn_tshift_fork: bool = True
     presoft: bool = True
+    shift3d_16: bool = True
 
     @staticmethod
     def from_env(env=None):
@@ -56,7 +60,8 @@ class Switches:
                         bn_shift2d=env.get("RK_BN_SHIFT2D", "1") != "0",
                         prepack=env.get("RK_PREPACK", "1") != "0",
                         bn_tshift_fork=env.get("RK_BN_TSHIFT_FORK", "1") != "0",
-                        presoft=env.get("RK_PRESOFT", "1") != "0")
+                        presoft=env.get("RK_PRESOFT", "1") != "0",
+                        shift3d_16=env.get("RK_SHIFT3D_16", "1") != "0")
 
 
 _current = Switches.from_env()

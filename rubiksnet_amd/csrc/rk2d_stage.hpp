@@ -20,33 +20,7 @@ using namespace dma;
 using dma2d::FDims;
 using g2d::Dims2;
 
-// 4 consecutive 16-bit elements <-> float4
-template <typename T> struct Cell4;
-template <> struct Cell4<__hip_bfloat16> {
-    __device__ static __forceinline__ float4 widen(const uint2& r) {
-        return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
-                           __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u));
-    }
-    __device__ static __forceinline__ unsigned bits(float v) {
-        return (unsigned)__builtin_bit_cast(unsigned short, __float2bfloat16(v));
-    }
-    __device__ static __forceinline__ uint2 narrow(float a, float b, float c, float d) {
-        return make_uint2(bits(a) | (bits(b) << 16), bits(c) | (bits(d) << 16));
-    }
-};
-template <> struct Cell4<__half> {
-    __device__ static __forceinline__ float4 widen(const uint2& r) {
-        const float2 lo = __half22float2(__builtin_bit_cast(__half2, r.x));
-        const float2 hi = __half22float2(__builtin_bit_cast(__half2, r.y));
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    }
-    __device__ static __forceinline__ unsigned bits(float v) {
-        return (unsigned)__builtin_bit_cast(unsigned short, __float2half(materialise(v)));
-    }
-    __device__ static __forceinline__ uint2 narrow(float a, float b, float c, float d) {
-        return make_uint2(bits(a) | (bits(b) << 16), bits(c) | (bits(d) << 16));
-    }
-};
+using rk::Cell4;              // (rk_common.hpp)
 
 __device__ __forceinline__ uint2 load_cell(const void* p) {
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));

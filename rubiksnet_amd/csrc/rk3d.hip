@@ -144,6 +144,62 @@ int backward_impl(const T* x, const T* shift, const T* gy, T* gx, T* gshift, int
     return run<T>(pl, c.d, o, stream);
 }
 
+// ---- 16-bit activations (bf16 / f16) next to an fp32 shift table: the kernels of rk3d_16.hip ----
+struct Ops16 {
+    const void* x; const float* shift; const void* gy; void* y; void* gx; float* gshift; float* ws;
+    int normalize; float t_factor;
+};
+int run16(const Plan& pl, const Dims3& d, bool bf16, const Ops16& o, rk_stream_t stream_) {
+    if (pl.rc) return pl.rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int i = 0; i < pl.n; ++i) {
+        const Launch& l = pl.l[i];
+        switch (l.family) {
+            case kStream16Fwd: s16::launch_stream_forward(l.c, l.g.s16, bf16, o.x, o.shift, o.y, stream); break;
+            case kStream16Bwd: s16::launch_stream_backward(l.c, l.g.s16, bf16, o.x, o.shift, o.gy, o.gx, o.ws, stream); break;
+            case kGen16Fwd: s16::launch_generic_forward(l.c, l.g.gen, bf16, o.x, o.shift, o.y, stream); break;
+            case kGen16BwdX: s16::launch_generic_backward_input(l.c, l.g.gen, bf16, o.shift, o.gy, o.gx, stream); break;
+            case kGen16BwdS: s16::launch_generic_backward_shift(l.c, l.g.gen, bf16, o.x, o.shift, o.gy, o.ws, stream); break;
+            case kFinalize:
+                hipLaunchKernelGGL((k3d_finalize<float>), dim3(l.c.grid), dim3(finalize_block(pl.P)), 0, stream, (const float*)o.ws,
+                                   o.gshift, d.C, pl.P, o.normalize, o.t_factor);
+                break;
+            default: break;
+        }
+    }
+    return launch_status();
+}
+int forward16_impl(bool bf16, const void* x, const float* shift, void* y, int N, int Tn, int C, int H, int W, int sT, int sH,
+                   int sW, int pT, int pH, int pW, int quantize, rk_stream_t stream) {
+    if (!x || !shift || !y) return RK_ERR_NULL_POINTER;
+    Call c{};
+    if (int rc = make_dims(c.d, N, Tn, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
+    c.form = kForward; c.elem = 2; c.quantize = quantize;
+    c.aligned = al(x, kAlX) | al(y, kAlY) | kAlGx;
+    Ops16 o{};
+    o.x = x; o.shift = shift; o.y = y;
+    return run16(plan(c, env_switches()), c.d, bf16, o, stream);
+}
+int backward16_impl(bool bf16, const void* x, const float* shift, const void* gy, void* gx, float* gshift, int N, int Tn, int C,
+                    int H, int W, int sT, int sH, int sW, int pT, int pH, int pW, int normalize_grad, float t_factor,
+                    int quantize, void* ws, size_t ws_bytes, rk_stream_t stream) {
+    if (!shift || !gy || (!gx && !gshift)) return RK_ERR_NULL_POINTER;
+    if (gshift && !x) return RK_ERR_NULL_POINTER;
+    Call c{};
+    if (int rc = make_dims(c.d, N, Tn, C, H, W, sT, sH, sW, pT, pH, pW)) return rc;
+    if (gshift) {
+        const size_t need = rk3d_backward_workspace_bytes(N, Tn, C, H, W, sT, sH, sW, pT, pH, pW, 2);
+        if (!ws || ws_bytes < need) return RK_ERR_WORKSPACE;
+    }
+    c.form = kBackward; c.elem = 2; c.quantize = quantize;
+    c.gx = gx; c.gshift = gshift;
+    c.aligned = al(x, kAlX) | al(gy, kAlY) | al(gx, kAlGx);
+    Ops16 o{};
+    o.x = x; o.shift = shift; o.gy = gy; o.gx = gx; o.gshift = gshift; o.ws = (float*)ws;
+    o.normalize = normalize_grad; o.t_factor = t_factor;
+    return run16(plan(c, env_switches()), c.d, bf16, o, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -161,7 +217,8 @@ size_t rk3d_backward_workspace_bytes(int N, int T, int C, int H, int W, int sT, 
     }
     const size_t P = (size_t)N * per_n;
     // fp32: the streaming backward keeps its partials as 16-byte granule pairs (rk_dma.hpp: fin_publish)
-    return (size_t)C * 3 * P * (size_t)(elem_size == 4 ? 16 : elem_size);
+    // 16-bit activations (elem_size 2): plain fp32 partials
+    return (size_t)C * 3 * P * (size_t)(elem_size == 4 ? 16 : elem_size == 2 ? 4 : elem_size);
 }
 
 // ---- training fusion: the shift applied to relu(bn(z)) without the activation ever being stored (train_block.py) ----
@@ -222,6 +279,36 @@ int rk3d_backward_f64(const double* x, const double* shift, const double* gy, do
                       rk_stream_t stream) {
     return backward_impl<double>(x, shift, gy, gx, gshift, N, T, C, H, W, sT, sH, sW, pT, pH, pW, normalize_grad,
                                  t_factor, quantize, ws, ws_bytes, stream);
+}
+
+int rk3d_forward_bf16_sf32(const void* x, const float* shift, void* y, int N, int T, int C, int H, int W, int sT, int sH,
+                           int sW, int pT, int pH, int pW, int quantize, rk_stream_t stream) {
+    return forward16_impl(true, x, shift, y, N, T, C, H, W, sT, sH, sW, pT, pH, pW, quantize, stream);
+}
+int rk3d_forward_f16_sf32(const void* x, const float* shift, void* y, int N, int T, int C, int H, int W, int sT, int sH,
+                          int sW, int pT, int pH, int pW, int quantize, rk_stream_t stream) {
+    return forward16_impl(false, x, shift, y, N, T, C, H, W, sT, sH, sW, pT, pH, pW, quantize, stream);
+}
+int rk3d_backward_bf16_sf32(const void* x, const float* shift, const void* gy, void* gx, float* gshift, int N, int T, int C,
+                            int H, int W, int sT, int sH, int sW, int pT, int pH, int pW, int normalize_grad, float t_factor,
+                            int quantize, void* ws, size_t ws_bytes, rk_stream_t stream) {
+    return backward16_impl(true, x, shift, gy, gx, gshift, N, T, C, H, W, sT, sH, sW, pT, pH, pW, normalize_grad, t_factor,
+                           quantize, ws, ws_bytes, stream);
+}
+int rk3d_backward_f16_sf32(const void* x, const float* shift, const void* gy, void* gx, float* gshift, int N, int T, int C,
+                           int H, int W, int sT, int sH, int sW, int pT, int pH, int pW, int normalize_grad, float t_factor,
+                           int quantize, void* ws, size_t ws_bytes, rk_stream_t stream) {
+    return backward16_impl(false, x, shift, gy, gx, gshift, N, T, C, H, W, sT, sH, sW, pT, pH, pW, normalize_grad, t_factor,
+                           quantize, ws, ws_bytes, stream);
+}
+// 1 when the streaming 16-bit kernels (rk3d_16.hpp) take the configuration, pointer alignment aside: a pure host predicate
+int rk3d_sf32_streams(int N, int T, int C, int H, int W, int sT, int sH, int sW, int pT, int pH, int pW, int quantize,
+                      int elem_size) {
+    Dims3 d;
+    if (elem_size != 2 || quantize || make_dims(d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return 0;
+    s16::SDims s;
+    Cfg3 c{};
+    return s16::geometry(s, c, d) ? 1 : 0;
 }
 
 // Two-phase form of the fp32 backward (the reference's own host glue has these phases, rubiks.cpp:324-376: K2 + K3/K4,

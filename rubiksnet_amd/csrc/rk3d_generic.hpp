@@ -76,10 +76,11 @@ __device__ __forceinline__ PlaneId my_plane(const Dims3& d, int planes_t /* To o
 }
 
 // ------------------------------------------------------------------------------ K1
-template <typename T, bool QUANT>
-__global__ __launch_bounds__(kBlock) void k3d_forward_generic(const T* __restrict__ x,
+// S: storage type of x / y (bf16 / f16 next to an fp32 shift table, T = float: widened on load, rounded once on store)
+template <typename T, bool QUANT, typename S = T>
+__global__ __launch_bounds__(kBlock) void k3d_forward_generic(const S* __restrict__ x,
                                                               const T* __restrict__ shift,
-                                                              T* __restrict__ y, Dims3 d) {
+                                                              S* __restrict__ y, Dims3 d) {
     int e;
     const PlaneId pl = my_plane(d, d.To, e);
     if (!pl.valid) return;
@@ -88,8 +89,8 @@ __global__ __launch_bounds__(kBlock) void k3d_forward_generic(const T* __restric
     const Frac<T> fW = split_shift(shift[2 * d.C + pl.c]);
     const int HW = d.H * d.W, HWo = d.Ho * d.Wo;
     const size_t tstride = (size_t)d.C * HW;
-    const T* xc = x + ((size_t)pl.n * d.T * d.C + pl.c) * HW;      // (n, t=0, c)
-    T* yp = y + (((size_t)pl.n * d.To + pl.t) * d.C + pl.c) * HWo;
+    const S* xc = x + ((size_t)pl.n * d.T * d.C + pl.c) * HW;      // (n, t=0, c)
+    S* yp = y + (((size_t)pl.n * d.To + pl.t) * d.C + pl.c) * HWo;
     const int bT = pl.t * d.sT - d.pT;
 
     int ho = e / d.Wo, wo = e - ho * d.Wo;
@@ -100,12 +101,12 @@ __global__ __launch_bounds__(kBlock) void k3d_forward_generic(const T* __restric
         const int qH = (fH.r < 0.5f) ? fH.fl : fH.fl + 1;
         const int qW = (fW.r < 0.5f) ? fW.fl : fW.fl + 1;
         const bool vt = tt >= 0 && tt < d.T;
-        const T* p = xc + (vt ? (size_t)tt * tstride : 0);
+        const S* p = xc + (vt ? (size_t)tt * tstride : 0);
         for (int i = e; i < HWo; i += d.E) {
             const int h = ho * d.sH - d.pH + qH, w = wo * d.sW - d.pW + qW;
             T v = 0;
-            if (vt && h >= 0 && h < d.H && w >= 0 && w < d.W) v = p[h * d.W + w];
-            yp[i] = v;
+            if (vt && h >= 0 && h < d.H && w >= 0 && w < d.W) v = ld(p + h * d.W + w);
+            st(yp + i, v);
             wo += dw; ho += dh;
             if (wo >= d.Wo) { wo -= d.Wo; ++ho; }
         }
@@ -114,8 +115,8 @@ __global__ __launch_bounds__(kBlock) void k3d_forward_generic(const T* __restric
 
     const int t0 = bT + fT.fl;
     const bool v0 = t0 >= 0 && t0 < d.T, v1 = t0 + 1 >= 0 && t0 + 1 < d.T;
-    const T* p0 = xc + (v0 ? (size_t)t0 * tstride : 0);
-    const T* p1 = xc + (v1 ? (size_t)(t0 + 1) * tstride : 0);
+    const S* p0 = xc + (v0 ? (size_t)t0 * tstride : 0);
+    const S* p1 = xc + (v1 ? (size_t)(t0 + 1) * tstride : 0);
     for (int i = e; i < HWo; i += d.E) {
         const int h0 = ho * d.sH - d.pH + fH.fl, w0 = wo * d.sW - d.pW + fW.fl;
         const bool mh0 = h0 >= 0 && h0 < d.H, mh1 = h0 + 1 >= 0 && h0 + 1 < d.H;
@@ -123,18 +124,18 @@ __global__ __launch_bounds__(kBlock) void k3d_forward_generic(const T* __restric
         const int o00 = h0 * d.W + w0;
         T q000 = 0, q001 = 0, q010 = 0, q011 = 0, q100 = 0, q101 = 0, q110 = 0, q111 = 0;
         if (v0) {
-            if (mh0 && mw0) q000 = p0[o00];
-            if (mh0 && mw1) q001 = p0[o00 + 1];
-            if (mh1 && mw0) q010 = p0[o00 + d.W];
-            if (mh1 && mw1) q011 = p0[o00 + d.W + 1];
+            if (mh0 && mw0) q000 = ld(p0 + o00);
+            if (mh0 && mw1) q001 = ld(p0 + o00 + 1);
+            if (mh1 && mw0) q010 = ld(p0 + o00 + d.W);
+            if (mh1 && mw1) q011 = ld(p0 + o00 + d.W + 1);
         }
         if (v1) {
-            if (mh0 && mw0) q100 = p1[o00];
-            if (mh0 && mw1) q101 = p1[o00 + 1];
-            if (mh1 && mw0) q110 = p1[o00 + d.W];
-            if (mh1 && mw1) q111 = p1[o00 + d.W + 1];
+            if (mh0 && mw0) q100 = ld(p1 + o00);
+            if (mh0 && mw1) q101 = ld(p1 + o00 + 1);
+            if (mh1 && mw0) q110 = ld(p1 + o00 + d.W);
+            if (mh1 && mw1) q111 = ld(p1 + o00 + d.W + 1);
         }
-        yp[i] = trilerp(q000, q001, q010, q011, q100, q101, q110, q111, fT.r, fH.r, fW.r);
+        st(yp + i, trilerp(q000, q001, q010, q011, q100, q101, q110, q111, fT.r, fH.r, fW.r));
         wo += dw; ho += dh;
         if (wo >= d.Wo) { wo -= d.Wo; ++ho; }
     }
@@ -151,16 +152,16 @@ __device__ __forceinline__ int unmap(int p, int s, int lim) {
 }
 
 // One input plane (n, t, c) of d(x), computed by the E threads e = 0..E-1 that call it.
-template <typename T, bool QUANT>
-__device__ __forceinline__ void backward_input_plane(const T* __restrict__ shift, const T* __restrict__ gy,
-                                                     T* __restrict__ gx, const Dims3& d, int n, int t, int c,
+template <typename T, bool QUANT, typename S = T>
+__device__ __forceinline__ void backward_input_plane(const T* __restrict__ shift, const S* __restrict__ gy,
+                                                     S* __restrict__ gx, const Dims3& d, int n, int t, int c,
                                                      int e, int E, int lo = 0, int hi = 0x7fffffff) {
     const T nT = -shift[c], nH = -shift[d.C + c], nW = -shift[2 * d.C + c];
     const Frac<T> fT = split_shift(nT), fH = split_shift(nH), fW = split_shift(nW);
     const int HW = d.H * d.W, HWo = d.Ho * d.Wo;
     const size_t tstride = (size_t)d.C * HWo;
-    const T* gc = gy + ((size_t)n * d.To * d.C + c) * HWo;   // (n, to=0, c)
-    T* gp = gx + (((size_t)n * d.T + t) * d.C + c) * HW;
+    const S* gc = gy + ((size_t)n * d.To * d.C + c) * HWo;   // (n, to=0, c)
+    S* gp = gx + (((size_t)n * d.T + t) * d.C + c) * HW;
     const int oT = t + d.pT;
 
     // elements lo + e, lo + e + E, ... below min(hi, HW): the whole plane by default, a sub-range for rk3d_slab.hpp
@@ -177,12 +178,12 @@ __device__ __forceinline__ void backward_input_plane(const T* __restrict__ shift
         const int aH = QUANT ? ((fH.r < 0.5f) ? fH.fl : fH.fl + 1) : 0;
         const int aW = QUANT ? ((fW.r < 0.5f) ? fW.fl : fW.fl + 1) : 0;
         const int tt = unmap(oT + aT, d.sT, d.To);
-        const T* p = gc + (tt >= 0 ? (size_t)tt * tstride : 0);
+        const S* p = gc + (tt >= 0 ? (size_t)tt * tstride : 0);
         for (int i = e; i < HWe; i += E) {
             const int hh = unmap(h + d.pH + aH, d.sH, d.Ho), ww = unmap(w + d.pW + aW, d.sW, d.Wo);
             T v = 0;
-            if (tt >= 0 && hh >= 0 && ww >= 0) v = p[hh * d.Wo + ww];
-            gp[i] = v;
+            if (tt >= 0 && hh >= 0 && ww >= 0) v = ld(p + hh * d.Wo + ww);
+            st(gp + i, v);
             w += dw; h += dh;
             if (w >= d.W) { w -= d.W; ++h; }
         }
@@ -190,38 +191,38 @@ __device__ __forceinline__ void backward_input_plane(const T* __restrict__ shift
     }
 
     const int t0 = unmap(oT + fT.fl, d.sT, d.To), t1 = unmap(oT + fT.fl + 1, d.sT, d.To);
-    const T* p0 = gc + (t0 >= 0 ? (size_t)t0 * tstride : 0);
-    const T* p1 = gc + (t1 >= 0 ? (size_t)t1 * tstride : 0);
+    const S* p0 = gc + (t0 >= 0 ? (size_t)t0 * tstride : 0);
+    const S* p1 = gc + (t1 >= 0 ? (size_t)t1 * tstride : 0);
     for (int i = e; i < HWe; i += E) {
         const int h0 = unmap(h + d.pH + fH.fl, d.sH, d.Ho), h1 = unmap(h + d.pH + fH.fl + 1, d.sH, d.Ho);
         const int w0 = unmap(w + d.pW + fW.fl, d.sW, d.Wo), w1 = unmap(w + d.pW + fW.fl + 1, d.sW, d.Wo);
         T q000 = 0, q001 = 0, q010 = 0, q011 = 0, q100 = 0, q101 = 0, q110 = 0, q111 = 0;
         if (t0 >= 0) {
-            if (h0 >= 0 && w0 >= 0) q000 = p0[h0 * d.Wo + w0];
-            if (h0 >= 0 && w1 >= 0) q001 = p0[h0 * d.Wo + w1];
-            if (h1 >= 0 && w0 >= 0) q010 = p0[h1 * d.Wo + w0];
-            if (h1 >= 0 && w1 >= 0) q011 = p0[h1 * d.Wo + w1];
+            if (h0 >= 0 && w0 >= 0) q000 = ld(p0 + h0 * d.Wo + w0);
+            if (h0 >= 0 && w1 >= 0) q001 = ld(p0 + h0 * d.Wo + w1);
+            if (h1 >= 0 && w0 >= 0) q010 = ld(p0 + h1 * d.Wo + w0);
+            if (h1 >= 0 && w1 >= 0) q011 = ld(p0 + h1 * d.Wo + w1);
         }
         if (t1 >= 0) {
-            if (h0 >= 0 && w0 >= 0) q100 = p1[h0 * d.Wo + w0];
-            if (h0 >= 0 && w1 >= 0) q101 = p1[h0 * d.Wo + w1];
-            if (h1 >= 0 && w0 >= 0) q110 = p1[h1 * d.Wo + w0];
-            if (h1 >= 0 && w1 >= 0) q111 = p1[h1 * d.Wo + w1];
+            if (h0 >= 0 && w0 >= 0) q100 = ld(p1 + h0 * d.Wo + w0);
+            if (h0 >= 0 && w1 >= 0) q101 = ld(p1 + h0 * d.Wo + w1);
+            if (h1 >= 0 && w0 >= 0) q110 = ld(p1 + h1 * d.Wo + w0);
+            if (h1 >= 0 && w1 >= 0) q111 = ld(p1 + h1 * d.Wo + w1);
         }
-        gp[i] = trilerp(q000, q001, q010, q011, q100, q101, q110, q111, fT.r, fH.r, fW.r);
+        st(gp + i, trilerp(q000, q001, q010, q011, q100, q101, q110, q111, fT.r, fH.r, fW.r));
         w += dw; h += dh;
         if (w >= d.W) { w -= d.W; ++h; }
     }
 }
 
-template <typename T, bool QUANT>
+template <typename T, bool QUANT, typename S = T>
 __global__ __launch_bounds__(kBlock) void k3d_backward_input_generic(const T* __restrict__ shift,
-                                                                     const T* __restrict__ gy,
-                                                                     T* __restrict__ gx, Dims3 d) {
+                                                                     const S* __restrict__ gy,
+                                                                     S* __restrict__ gx, Dims3 d) {
     int e;
     const PlaneId pl = my_plane(d, d.T, e);   // planes of the INPUT
     if (!pl.valid) return;
-    backward_input_plane<T, QUANT>(shift, gy, gx, d, pl.n, pl.t, pl.c, e, d.E);
+    backward_input_plane<T, QUANT, S>(shift, gy, gx, d, pl.n, pl.t, pl.c, e, d.E);
 }
 
 // ------------------------------------------------------------------------------ K2
@@ -239,9 +240,9 @@ struct BnAct {
     float a, b;
     __device__ __forceinline__ float operator()(float v) const { return fmaxf(fmaf(a, v, b), 0.f); }
 };
-template <typename T, typename Act = NoAct>
-__device__ __forceinline__ void shift_grad_plane(const T* __restrict__ x, const T* __restrict__ shift,
-                                                 const T* __restrict__ gy, const Dims3& d, int n, int to, int c,
+template <typename T, typename Act = NoAct, typename S = T>
+__device__ __forceinline__ void shift_grad_plane(const S* __restrict__ x, const T* __restrict__ shift,
+                                                 const S* __restrict__ gy, const Dims3& d, int n, int to, int c,
                                                  int e, int E, T& aT, T& aH, T& aW, const Act act = Act(),
                                                  int lo = 0, int hi = 0x7fffffff) {
     const Frac<T> fT = split_shift(shift[c]);
@@ -250,13 +251,13 @@ __device__ __forceinline__ void shift_grad_plane(const T* __restrict__ x, const 
     const int zT = (fT.r == 0) ? 1 : 0, zH = (fH.r == 0) ? 1 : 0, zW = (fW.r == 0) ? 1 : 0;
     const int HW = d.H * d.W, HWo = d.Ho * d.Wo;
     const size_t tstride = (size_t)d.C * HW;
-    const T* xc = x + ((size_t)n * d.T * d.C + c) * HW;
-    const T* gp = gy + (((size_t)n * d.To + to) * d.C + c) * HWo;
+    const S* xc = x + ((size_t)n * d.T * d.C + c) * HW;
+    const S* gp = gy + (((size_t)n * d.To + to) * d.C + c) * HWo;
     const int bT = to * d.sT - d.pT;
     const int t0 = bT + fT.fl - zT, t1 = bT + fT.fl + 1;
     const bool v0 = t0 >= 0 && t0 < d.T, v1 = t1 >= 0 && t1 < d.T;
-    const T* p0 = xc + (v0 ? (size_t)t0 * tstride : 0);
-    const T* p1 = xc + (v1 ? (size_t)t1 * tstride : 0);
+    const S* p0 = xc + (v0 ? (size_t)t0 * tstride : 0);
+    const S* p1 = xc + (v1 ? (size_t)t1 * tstride : 0);
 
     e += lo;                                              // output elements lo + e, lo + e + E, ... below min(hi, HWo)
     const int HWe = hi < HWo ? hi : HWo;
@@ -269,16 +270,16 @@ __device__ __forceinline__ void shift_grad_plane(const T* __restrict__ x, const 
         const bool mw0 = w0 >= 0 && w0 < d.W, mw1 = w1 >= 0 && w1 < d.W;
         T q000 = 0, q001 = 0, q010 = 0, q011 = 0, q100 = 0, q101 = 0, q110 = 0, q111 = 0;
         if (v0) {
-            if (mh0 && mw0) q000 = act(p0[h0 * d.W + w0]);
-            if (mh0 && mw1) q001 = act(p0[h0 * d.W + w1]);
-            if (mh1 && mw0) q010 = act(p0[h1 * d.W + w0]);
-            if (mh1 && mw1) q011 = act(p0[h1 * d.W + w1]);
+            if (mh0 && mw0) q000 = act(ld(p0 + h0 * d.W + w0));
+            if (mh0 && mw1) q001 = act(ld(p0 + h0 * d.W + w1));
+            if (mh1 && mw0) q010 = act(ld(p0 + h1 * d.W + w0));
+            if (mh1 && mw1) q011 = act(ld(p0 + h1 * d.W + w1));
         }
         if (v1) {
-            if (mh0 && mw0) q100 = act(p1[h0 * d.W + w0]);
-            if (mh0 && mw1) q101 = act(p1[h0 * d.W + w1]);
-            if (mh1 && mw0) q110 = act(p1[h1 * d.W + w0]);
-            if (mh1 && mw1) q111 = act(p1[h1 * d.W + w1]);
+            if (mh0 && mw0) q100 = act(ld(p1 + h0 * d.W + w0));
+            if (mh0 && mw1) q101 = act(ld(p1 + h0 * d.W + w1));
+            if (mh1 && mw0) q110 = act(ld(p1 + h1 * d.W + w0));
+            if (mh1 && mw1) q111 = act(ld(p1 + h1 * d.W + w1));
         }
         const T Ts = interp2(q000, q001, q010, q011, fH.r, fW.r);
         const T Tl = interp2(q100, q101, q110, q111, fH.r, fW.r);
@@ -286,7 +287,7 @@ __device__ __forceinline__ void shift_grad_plane(const T* __restrict__ x, const 
         const T Hl = interp2(q010, q011, q110, q111, fT.r, fW.r);
         const T Ws = interp2(q000, q010, q100, q110, fT.r, fH.r);
         const T Wl = interp2(q001, q011, q101, q111, fT.r, fH.r);
-        const T up = gp[i];
+        const T up = ld(gp + i);
         aT += (-Ts + Tl) * up;
         aH += (-Hs + Hl) * up;
         aW += (-Ws + Wl) * up;
@@ -295,16 +296,16 @@ __device__ __forceinline__ void shift_grad_plane(const T* __restrict__ x, const 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k3d_backward_shift_generic(const T* __restrict__ x,
+template <typename T, typename S = T>
+__global__ __launch_bounds__(kBlock) void k3d_backward_shift_generic(const S* __restrict__ x,
                                                                      const T* __restrict__ shift,
-                                                                     const T* __restrict__ gy,
+                                                                     const S* __restrict__ gy,
                                                                      T* __restrict__ part, Dims3 d) {
     __shared__ T red[3][kBlock / kWave];
     int e;
     const PlaneId pl = my_plane(d, d.To, e);
     T aT = 0, aH = 0, aW = 0;
-    if (pl.valid) shift_grad_plane<T>(x, shift, gy, d, pl.n, pl.t, pl.c, e, d.E, aT, aH, aW);
+    if (pl.valid) shift_grad_plane<T, NoAct, S>(x, shift, gy, d, pl.n, pl.t, pl.c, e, d.E, aT, aH, aW);
     aT = group_sum(aT, d.E, red[0]);
     aH = group_sum(aH, d.E, red[1]);
     aW = group_sum(aW, d.E, red[2]);

@@ -12,13 +12,15 @@
 #include "rk3d_stride2.hpp"
 #include "rk3d_column.hpp"
 #include "rk3d_slab.hpp"
+#include "rk3d_16.hpp"
 
 namespace rk {
 namespace plan3d {
 
 enum Family {                 // the kernel template of a launch; Cfg3::v holds its variant
     kNone, kPlane, kDmaInterp, kDmaBwd, kTileInterp, kTileBwd, kSlabInterp, kSlabBwd, kXlate, kS2Fwd, kS2Bwd, kSlabS2Fwd,
-    kSlabS2Bwd, kColFwd, kColBwd, kGenFwd, kGenBwdX, kGenBwdS, kFinalize
+    kSlabS2Bwd, kColFwd, kColBwd, kGenFwd, kGenBwdX, kGenBwdS, kFinalize,
+    kGen16Fwd, kGen16BwdX, kGen16BwdS, kStream16Fwd, kStream16Bwd          // 16-bit activations, fp32 shift (rk3d_16.hpp)
 };
 enum Form { kForward, kBackward, kForwardBn, kBackwardBn };
 enum Aligned { kAlX = 1, kAlY = 2, kAlGx = 4, kAlBn = 8 };     // 16-byte aligned: x / z, y (forward) or gy, gx / dz, the BN pack
@@ -32,17 +34,17 @@ struct Switches { ShiftKernels kernels; int slab14; };
 struct Call {
     Dims3 d;
     Form form;
-    int elem;                 // 4: fp32, 8: fp64
+    int elem;                 // 4: fp32, 8: fp64, 2: bf16 / f16 activations next to an fp32 shift table (rk3d_*_sf32)
     bool quantize, gx, gshift, two_phase;     // backward: the gradients wanted; two_phase: stop after the partials
     int aligned;              // Aligned bits; an operand the call does not have counts as aligned
 };
 struct Launch {
     Family family;
     Cfg3 c;
-    union { plane3d::PDims plane; dma::BDims band; s2::SDims s2; slab3d::SDims slab; slab3d::S2Dims slab2; col3d::CDims col; Dims3 gen; } g;
+    union { plane3d::PDims plane; dma::BDims band; s2::SDims s2; slab3d::SDims slab; slab3d::S2Dims slab2; col3d::CDims col; Dims3 gen; s16::SDims s16; } g;
 };
 struct Plan {
-    int rc;                   // RK_OK, or RK_ERR_UNSUPPORTED (the BN forms: no fused kernel covers the call)
+    int rc;                   // RK_OK, or RK_ERR_UNSUPPORTED (the BN forms: no fused kernel covers the call; 16-bit: no such form)
     int n;
     Launch l[3];              // in launch order; a separate finalize (k3d_finalize) is the last of them
     int P;                    // partials per channel and sum of the d(shift) launch: ws[C][3 or 5][P]; 0: no d(shift)
@@ -64,6 +66,41 @@ inline Plan plan(const Call& c, const Switches& sw) {
     Plan pl{};
     auto variant = [](int v0, int v1) { Launch l{}; l.c.v[0] = v0; l.c.v[1] = v1; return l; };
     auto take = [&pl](Family f, Launch& l) { l.family = f; pl.l[pl.n++] = l; return true; };
+    auto generic = [&](Family f, int quant, int plane_elems, int planes_t) {
+        Launch l = variant(quant, 0);
+        l.g.gen = d;
+        set_group(l.g.gen, plane_elems);
+        l.c.grid = grid_for(l.g.gen, (long long)d.N * planes_t * d.C);
+        return take(f, l);
+    };
+    auto finalize = [&] {                                              // k3d_finalize: row-sum of the P partials per channel + K5
+        Launch l = variant(0, 0);
+        l.c.grid = (unsigned)d.C;
+        pl.finalize = true;
+        return take(kFinalize, l);
+    };
+    if (c.elem == 2) {
+        // 16-bit activations: the streaming kernels of rk3d_16.hpp where they apply and every operand they touch is 16-byte
+        // aligned, else the generic plane kernels at 16-bit storage; fp32 partials, the finalize always a launch of its own.
+        // No BN form, no two-phase form.
+        if (c.form == kForwardBn || c.form == kBackwardBn || c.two_phase) return pl.rc = RK_ERR_UNSUPPORTED, pl;
+        const bool al16 = (c.aligned & (kAlX | kAlY | kAlGx)) == (kAlX | kAlY | kAlGx);
+        Launch l = variant(c.form == kBackward && c.gx, c.form == kBackward && c.gshift);
+        const bool streams = !c.quantize && sw.kernels == ShiftKernels::Auto && al16 && s16::geometry(l.g.s16, l.c, d);
+        if (c.form == kForward) return (streams ? take(kStream16Fwd, l) : generic(kGen16Fwd, c.quantize, d.Ho * d.Wo, d.To)), pl;
+        if (streams) {
+            take(kStream16Bwd, l);
+            if (c.gshift) pl.P = d.N * l.g.s16.bands;
+        } else {
+            if (c.gx) generic(kGen16BwdX, c.quantize, d.H * d.W, d.T);
+            if (c.gshift) {
+                generic(kGen16BwdS, 0, d.Ho * d.Wo, d.To);
+                pl.P = d.N * d.To;
+            }
+        }
+        if (c.gshift) finalize();
+        return pl;
+    }
     const bool f32 = c.elem == 4, bn = c.form == kForwardBn || c.form == kBackwardBn;
     const bool streaming = f32 && sw.kernels == ShiftKernels::Auto, column = sw.kernels != ShiftKernels::Generic;
     const bool band_ok = s1p0(d) && d.W % 4 == 0 && d.W >= 4;                   // rk3d_plane.hpp, rk3d_dma.hpp
@@ -127,13 +164,6 @@ inline Plan plan(const Call& c, const Switches& sw) {
         }
         return slab && slab3d::geometry_s2(l.g.slab2, l.c, d, true) && done(kSlabS2Bwd, 2 * d.N);   // 28 -> 14 and 14 -> 7
     };
-    auto generic = [&](Family f, int quant, int plane_elems, int planes_t) {
-        Launch l = variant(quant, 0);
-        l.g.gen = d;
-        set_group(l.g.gen, plane_elems);
-        l.c.grid = grid_for(l.g.gen, (long long)d.N * planes_t * d.C);
-        return take(f, l);
-    };
     const bool col_ok = column && !c.quantize && d.sT == 1 && d.pT == 0;   // rk3d_column.hpp
 
     switch (c.form) {
@@ -185,11 +215,7 @@ inline Plan plan(const Call& c, const Switches& sw) {
             pl.finalize = !c.two_phase;
         }
     }
-    if (pl.finalize) {                                                 // k3d_finalize: row-sum of the P partials per channel + K5
-        Launch l = variant(0, 0);
-        l.c.grid = (unsigned)d.C;
-        take(kFinalize, l);
-    }
+    if (pl.finalize) finalize();
     return pl;
 }
 

@@ -35,6 +35,34 @@ template <> __device__ __forceinline__ void st<__hip_bfloat16>(__hip_bfloat16* p
     *p = __float2bfloat16(v);
 }
 
+// 4 consecutive 16-bit elements <-> float4 (the 16-bit streaming kernels, 2-D and 3-D: one rounding, on store)
+template <typename T> struct Cell4;
+template <> struct Cell4<__hip_bfloat16> {
+    __device__ static __forceinline__ float4 widen(const uint2& r) {
+        return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
+                           __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u));
+    }
+    __device__ static __forceinline__ unsigned bits(float v) {
+        return (unsigned)__builtin_bit_cast(unsigned short, __float2bfloat16(v));
+    }
+    __device__ static __forceinline__ uint2 narrow(float a, float b, float c, float d) {
+        return make_uint2(bits(a) | (bits(b) << 16), bits(c) | (bits(d) << 16));
+    }
+};
+template <> struct Cell4<__half> {
+    __device__ static __forceinline__ float4 widen(const uint2& r) {
+        const float2 lo = __half22float2(__builtin_bit_cast(__half2, r.x));
+        const float2 hi = __half22float2(__builtin_bit_cast(__half2, r.y));
+        return make_float4(lo.x, lo.y, hi.x, hi.y);
+    }
+    __device__ static __forceinline__ unsigned bits(float v) {
+        return (unsigned)__builtin_bit_cast(unsigned short, __float2half(materialise(v)));
+    }
+    __device__ static __forceinline__ uint2 narrow(float a, float b, float c, float d) {
+        return make_uint2(bits(a) | (bits(b) << 16), bits(c) | (bits(d) << 16));
+    }
+};
+
 // ---- wave / block reductions (deterministic: fixed tree, no float atomics) -------
 // Sum over the 64 lanes, returned in EVERY lane.  float / double: DPP row shifts + row broadcasts (the gfx9 reduction
 // idiom: 4 steps inside each row of 16 lanes, row_bcast:15, row_bcast:31, then lane 63 read back) -- a handful of VALU

@@ -147,6 +147,92 @@ def rubiks_shift_3d_backward_double(input, shift, output_grad, strides, paddings
                        shift_grad, normalize_grad, normalize_t_factor, quantize)
 
 
+_SFX16 = {torch.bfloat16: "bf16_sf32", torch.float16: "f16_sf32"}
+
+
+def _dtype16(input):
+    if not torch.is_tensor(input) or input.dtype not in _SFX16:
+        raise ValueError("the *_sf32 3-D operators take bfloat16 or float16 activations next to a float32 shift")
+    return input.dtype
+
+
+def _forward3d16(input, shift, strides, paddings, quantize, output):
+    dt = _dtype16(input)
+    _require(input, "input", dt); _require(shift, "shift", torch.float32); _require(output, "output", dt)
+    dev = _same_device(input, shift, output)
+    s, p = _ints(strides, 3, "strides"), _ints(paddings, 3, "paddings")
+    if input.dim() != 5:
+        raise RuntimeError("input must be [N,T,C,H,W]")
+    N, T, C, H, W = input.shape
+    if tuple(shift.shape) != (3, C):
+        raise RuntimeError("shift must be [3, %d], got %s" % (C, tuple(shift.shape)))
+    L = _native.lib()
+    want = (N, L.rk_out_len(T, s[0], p[0]), C, L.rk_out_len(H, s[1], p[1]), L.rk_out_len(W, s[2], p[2]))
+    if tuple(output.shape) != want:
+        raise RuntimeError("output has shape %s, expected %s" % (tuple(output.shape), want))
+    if input.numel() == 0 or output.numel() == 0:
+        return 0
+    name = "rk3d_forward_" + _SFX16[dt]
+    with torch.cuda.device(dev):
+        rc = getattr(L, name)(input.data_ptr(), shift.data_ptr(), output.data_ptr(), N, T, C, H, W, *s, *p,
+                              int(bool(quantize)), _stream_ptr(dev))
+    _native.check(rc, name)
+    return 0
+
+
+def _backward3d16(input, shift, output_grad, strides, paddings, input_grad, shift_grad, normalize_grad,
+                  normalize_t_factor, quantize):
+    dt = _dtype16(input)
+    _require(input, "input", dt); _require(shift, "shift", torch.float32)
+    _require(output_grad, "output_grad", dt)
+    if input_grad is not None:
+        _require(input_grad, "input_grad", dt)
+    if shift_grad is not None:
+        _require(shift_grad, "shift_grad", torch.float32)
+    dev = _same_device(input, shift, output_grad)
+    s, p = _ints(strides, 3, "strides"), _ints(paddings, 3, "paddings")
+    N, T, C, H, W = input.shape
+    L = _native.lib()
+    # (no in-launch finalizer in these kernels: the give-up record, fin_status, is not involved)
+    want = (N, L.rk_out_len(T, s[0], p[0]), C, L.rk_out_len(H, s[1], p[1]), L.rk_out_len(W, s[2], p[2]))
+    if tuple(output_grad.shape) != want:
+        raise RuntimeError("output_grad has shape %s, expected %s" % (tuple(output_grad.shape), want))
+    if input_grad is not None and input_grad.shape != input.shape:
+        raise RuntimeError("input_grad must have the shape of input")
+    if shift_grad is not None and tuple(shift_grad.shape) != (3, C):
+        raise RuntimeError("shift_grad must be [3, C]")
+    if input.numel() == 0 or output_grad.numel() == 0:
+        if shift_grad is not None:
+            shift_grad.zero_()
+        return 0
+    name = "rk3d_backward_" + _SFX16[dt]
+    with torch.cuda.device(dev):
+        ws_bytes = L.rk3d_backward_workspace_bytes(N, T, C, H, W, *s, *p, 2) if shift_grad is not None else 0
+        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev) if shift_grad is not None else None
+        rc = getattr(L, name)(
+            input.data_ptr(), shift.data_ptr(), output_grad.data_ptr(),
+            input_grad.data_ptr() if input_grad is not None else None,
+            shift_grad.data_ptr() if shift_grad is not None else None,
+            N, T, C, H, W, *s, *p, int(bool(normalize_grad)), float(normalize_t_factor),
+            int(bool(quantize)), ws.data_ptr() if ws is not None else None, int(ws_bytes), _stream_ptr(dev))
+    _native.check(rc, name)
+    return 0
+
+
+def rubiks_shift_3d_forward_sf32(input, shift, strides, paddings, quantize, output):
+    """RubiksShift3D forward on bfloat16 / float16 activations with a float32 shift table (rk3d_forward_*_sf32): fp32
+    arithmetic on the un-rounded shift, one rounding on store.  An addition (not in __all__): the reference has no such op."""
+    return _forward3d16(input, shift, strides, paddings, quantize, output)
+
+
+def rubiks_shift_3d_backward_sf32(input, shift, output_grad, strides, paddings, input_grad, shift_grad,
+                                  normalize_grad, normalize_t_factor, quantize):
+    """The backward of rubiks_shift_3d_forward_sf32: input_grad in the activations' dtype, shift_grad float32; either may
+    be None to skip that half (no workspace is taken when shift_grad is None)."""
+    return _backward3d16(input, shift, output_grad, strides, paddings, input_grad, shift_grad, normalize_grad,
+                         normalize_t_factor, quantize)
+
+
 def _sfx2d(t, shift):
     """Entry-point suffix and the dtype the shift table / d(shift) must have.  The reference runs K6-K9 at the
     tensor's own scalar type, shift included (rubiks2d_kernels.cu:113-114); next to 16-bit activations an fp32

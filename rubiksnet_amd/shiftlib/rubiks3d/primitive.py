@@ -14,7 +14,7 @@ x is [N, T, C, H, W] (NOT NCTHW), shift is [3, C] with rows (T, H, W).
 """
 import torch
 
-from rubiksnet_amd import _native, rubiksnet_cuda
+from rubiksnet_amd import _native, config, rubiksnet_cuda
 from rubiksnet_amd.utils import allocate_output, make_tuple
 
 __all__ = [
@@ -151,6 +151,49 @@ class RubiksShift3DFunc(torch.autograd.Function):
         return x_grad, shift_grad, None, None, None, None, None
 
 
+class RubiksShift3D16Func(torch.autograd.Function):
+    """The same node on 16-bit activations next to an fp32 shift (rubiksnet_cuda.rubiks_shift_3d_*_sf32): saves the 16-bit
+    x and the fp32 shift, returns d(x) in x's dtype and d(shift) in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, shift, stride, padding, normalize_grad, normalize_t_factor, quantize):
+        assert isinstance(normalize_grad, bool)
+        ctx.stride = _per_axis(stride)
+        ctx.padding = _per_axis(padding)
+        ctx.normalize_grad = normalize_grad
+        ctx.normalize_t_factor = normalize_t_factor
+        ctx.quantize = quantize
+        x = x.contiguous()
+        shift = shift.contiguous()
+        ctx.save_for_backward(x, shift)
+        y = x.new_empty(compute_output_shape(x, ctx.stride, ctx.padding, shift_dim=_DIM))
+        rubiksnet_cuda.rubiks_shift_3d_forward_sf32(x, shift, ctx.stride, ctx.padding, quantize, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        x, shift = ctx.saved_tensors
+        x_grad = shift_grad = None
+        if any(ctx.needs_input_grad[:2]):
+            x_grad = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            shift_grad = torch.empty_like(shift) if ctx.needs_input_grad[1] else None
+            rubiksnet_cuda.rubiks_shift_3d_backward_sf32(
+                x, shift, grad_output.contiguous(), ctx.stride, ctx.padding, x_grad, shift_grad, ctx.normalize_grad,
+                ctx.normalize_t_factor, ctx.quantize)
+        return x_grad, shift_grad, None, None, None, None, None
+
+
+def _native16(x, shift, stride, padding, quantize):
+    """True when the 16-bit kernels take this call: bf16 / f16 activations next to an fp32 shift, RK_SHIFT3D_16 on, and a
+    configuration of the streaming 16-bit family (rk3d_sf32_streams) -- the ones measured faster than the cast path."""
+    if shift.dtype != torch.float32 or not x.is_cuda or not config.switches().shift3d_16:
+        return False
+    if x.numel() == 0:
+        return False
+    dims = [int(v) for v in x.size()] + list(_per_axis(stride)) + list(_per_axis(padding))
+    return _native.lib().rk3d_sf32_streams(*dims, int(bool(quantize)), 2) == 1
+
+
 def rubiks_shift_3d(x, shift, stride=1, padding=0, normalize_grad=True, normalize_t_factor=1.0, quantize=False):
     """User-facing functional (rubiks3d/primitive.py:193-215)."""
     assert len(x.size()) == 5, "x must be [N, T, C, H, W]"
@@ -161,6 +204,8 @@ def rubiks_shift_3d(x, shift, stride=1, padding=0, normalize_grad=True, normaliz
     else:
         assert isinstance(normalize_t_factor, (int, float))
     if x.dtype in (torch.float16, torch.bfloat16):
+        if _native16(x, shift, stride, padding, quantize):
+            return RubiksShift3D16Func.apply(x, shift, stride, padding, normalize_grad, normalize_t_factor, quantize)
         # autocast hands half activations to an fp32 parameter.  The reference's 3D op exists in fp32/fp64 only
         # (primitive.py:66-75): run it in fp32 and hand back the caller's dtype (the explicit-dtype primitives
         # below still raise for half inputs, as the reference does).
