@@ -191,9 +191,9 @@ int rk3d_backward_finalize_f32(const void* workspace, int C, int partials, float
  * narrowed -- quantize included.  gshift is summed in fp32 per partial, then in a fixed order in fp64 per channel, as in
  * the fp32 operator; normalize_grad / normalize_t_factor as there.  gx or gshift may be NULL to skip that half; the
  * workspace (needed for gshift only) is the one for elem_size = 2.  Validation order and error codes as the fp32 entry
- * points.  Stride (1,1,1) / pad 0 / quantize off configurations whose slabs of G planes are whole 16-byte chunks run on the
- * streaming kernels when every tensor is 16-byte aligned (csrc/rk3d_16.hip); everything else runs on the per-plane kernels
- * at 16-bit storage.  No BatchNorm-fused and no two-phase form exists for these types. */
+ * points.  Pad 0 / quantize off configurations at stride (1,1,1), or at stride (1,2,2) with W % 8 == 0 and even H, whose
+ * slabs of G planes are whole 16-byte chunks run on the streaming kernels when every tensor is 16-byte aligned
+ * (csrc/rk3d_16.hip); everything else runs on the per-plane kernels at 16-bit storage.  No BatchNorm-fused and no two-phase form exists for these types. */
 int rk3d_forward_bf16_sf32(const void* x, const float* shift, void* y,
                            int N, int T, int C, int H, int W,
                            int stride_T, int stride_H, int stride_W,
@@ -218,7 +218,7 @@ int rk3d_backward_f16_sf32(const void* x, const float* shift, const void* gy,
                            int pad_T, int pad_H, int pad_W,
                            int normalize_grad, float normalize_t_factor, int quantize,
                            void* workspace, size_t workspace_bytes, rk_stream_t stream);
-/* 1 when the streaming 16-bit kernels take the configuration (elem_size must be 2), pointer alignment aside, else 0.  A
+/* 1 when the streaming 16-bit kernels (either stride class) take the configuration (elem_size must be 2), pointer alignment aside, else 0.  A
  * pure host predicate, no device call: the Python layer routes autocast activations to the entry points above where it
  * says 1 and keeps the fp32 operator between two casts elsewhere. */
 int rk3d_sf32_streams(int N, int T, int C, int H, int W,

@@ -17,8 +17,8 @@
     RK_PRESOFT     1 | 0          train step: the [C, 3] tap softmax of every AttentionShift layer in one launch each way
                                   (attention_shift.presoftened) / one launch per layer and direction
     RK_SHIFT3D_16  1 | 0          bf16 / f16 activations next to an fp32 shift table (autocast): RubiksShift3D runs natively on
-                                  the 16-bit tensors (rk3d_*_sf32) wherever the streaming 16-bit kernels take the layer
-                                  (rk3d_sf32_streams) / everywhere the fp32 operator between two casts
+                                  the 16-bit tensors (rk3d_*_sf32) wherever the streaming 16-bit kernels, stride 1 or
+                                  stride (1,2,2), take the layer (rk3d_sf32_streams) / everywhere the fp32 operator between two casts
 
 Everything else that used to be tunable from the environment (tile shapes, channel limits, prefetch depths)
 is a constant next to the code it tunes.  The native library reads its own switches once per process

@@ -157,6 +157,8 @@ int run16(const Plan& pl, const Dims3& d, bool bf16, const Ops16& o, rk_stream_t
         switch (l.family) {
             case kStream16Fwd: s16::launch_stream_forward(l.c, l.g.s16, bf16, o.x, o.shift, o.y, stream); break;
             case kStream16Bwd: s16::launch_stream_backward(l.c, l.g.s16, bf16, o.x, o.shift, o.gy, o.gx, o.ws, stream); break;
+            case kStream16S2Fwd: s16::launch_s2_forward(l.c, l.g.s16s2, bf16, o.x, o.shift, o.y, stream); break;
+            case kStream16S2Bwd: s16::launch_s2_backward(l.c, l.g.s16s2, bf16, o.x, o.shift, o.gy, o.gx, o.ws, stream); break;
             case kGen16Fwd: s16::launch_generic_forward(l.c, l.g.gen, bf16, o.x, o.shift, o.y, stream); break;
             case kGen16BwdX: s16::launch_generic_backward_input(l.c, l.g.gen, bf16, o.shift, o.gy, o.gx, stream); break;
             case kGen16BwdS: s16::launch_generic_backward_shift(l.c, l.g.gen, bf16, o.x, o.shift, o.gy, o.ws, stream); break;
@@ -301,14 +303,16 @@ int rk3d_backward_f16_sf32(const void* x, const float* shift, const void* gy, vo
     return backward16_impl(false, x, shift, gy, gx, gshift, N, T, C, H, W, sT, sH, sW, pT, pH, pW, normalize_grad, t_factor,
                            quantize, ws, ws_bytes, stream);
 }
-// 1 when the streaming 16-bit kernels (rk3d_16.hpp) take the configuration, pointer alignment aside: a pure host predicate
+// 1 when one of the streaming 16-bit families (rk3d_16.hpp: stride 1, stride (1,2,2)) takes the configuration, pointer
+// alignment aside: a pure host predicate
 int rk3d_sf32_streams(int N, int T, int C, int H, int W, int sT, int sH, int sW, int pT, int pH, int pW, int quantize,
                       int elem_size) {
     Dims3 d;
     if (elem_size != 2 || quantize || make_dims(d, N, T, C, H, W, sT, sH, sW, pT, pH, pW)) return 0;
     s16::SDims s;
+    s16::S2Dims s2;
     Cfg3 c{};
-    return s16::geometry(s, c, d) ? 1 : 0;
+    return s16::geometry(s, c, d) || s16::geometry_s2(s2, c, d, false) ? 1 : 0;
 }
 
 // Two-phase form of the fp32 backward (the reference's own host glue has these phases, rubiks.cpp:324-376: K2 + K3/K4,

@@ -20,7 +20,8 @@ namespace plan3d {
 enum Family {                 // the kernel template of a launch; Cfg3::v holds its variant
     kNone, kPlane, kDmaInterp, kDmaBwd, kTileInterp, kTileBwd, kSlabInterp, kSlabBwd, kXlate, kS2Fwd, kS2Bwd, kSlabS2Fwd,
     kSlabS2Bwd, kColFwd, kColBwd, kGenFwd, kGenBwdX, kGenBwdS, kFinalize,
-    kGen16Fwd, kGen16BwdX, kGen16BwdS, kStream16Fwd, kStream16Bwd          // 16-bit activations, fp32 shift (rk3d_16.hpp)
+    kGen16Fwd, kGen16BwdX, kGen16BwdS, kStream16Fwd, kStream16Bwd,         // 16-bit activations, fp32 shift (rk3d_16.hpp)
+    kStream16S2Fwd, kStream16S2Bwd                                         // ... their stride (1,2,2) streaming family
 };
 enum Form { kForward, kBackward, kForwardBn, kBackwardBn };
 enum Aligned { kAlX = 1, kAlY = 2, kAlGx = 4, kAlBn = 8 };     // 16-byte aligned: x / z, y (forward) or gy, gx / dz, the BN pack
@@ -41,7 +42,7 @@ struct Call {
 struct Launch {
     Family family;
     Cfg3 c;
-    union { plane3d::PDims plane; dma::BDims band; s2::SDims s2; slab3d::SDims slab; slab3d::S2Dims slab2; col3d::CDims col; Dims3 gen; s16::SDims s16; } g;
+    union { plane3d::PDims plane; dma::BDims band; s2::SDims s2; slab3d::SDims slab; slab3d::S2Dims slab2; col3d::CDims col; Dims3 gen; s16::SDims s16; s16::S2Dims s16s2; } g;
 };
 struct Plan {
     int rc;                   // RK_OK, or RK_ERR_UNSUPPORTED (the BN forms: no fused kernel covers the call; 16-bit: no such form)
@@ -80,17 +81,25 @@ inline Plan plan(const Call& c, const Switches& sw) {
         return take(kFinalize, l);
     };
     if (c.elem == 2) {
-        // 16-bit activations: the streaming kernels of rk3d_16.hpp where they apply and every operand they touch is 16-byte
-        // aligned, else the generic plane kernels at 16-bit storage; fp32 partials, the finalize always a launch of its own.
-        // No BN form, no two-phase form.
+        // 16-bit activations: the streaming kernels of rk3d_16.hpp (stride 1, or stride (1,2,2)) where they apply and every
+        // operand they touch is 16-byte aligned, else the generic plane kernels at 16-bit storage; fp32 partials, the finalize
+        // always a launch of its own.  No BN form, no two-phase form.
         if (c.form == kForwardBn || c.form == kBackwardBn || c.two_phase) return pl.rc = RK_ERR_UNSUPPORTED, pl;
         const bool al16 = (c.aligned & (kAlX | kAlY | kAlGx)) == (kAlX | kAlY | kAlGx);
         Launch l = variant(c.form == kBackward && c.gx, c.form == kBackward && c.gshift);
-        const bool streams = !c.quantize && sw.kernels == ShiftKernels::Auto && al16 && s16::geometry(l.g.s16, l.c, d);
-        if (c.form == kForward) return (streams ? take(kStream16Fwd, l) : generic(kGen16Fwd, c.quantize, d.Ho * d.Wo, d.To)), pl;
-        if (streams) {
-            take(kStream16Bwd, l);
-            if (c.gshift) pl.P = d.N * l.g.s16.bands;
+        const bool may = !c.quantize && sw.kernels == ShiftKernels::Auto && al16;
+        const bool streams = may && s16::geometry(l.g.s16, l.c, d);                                   // stride 1
+        const bool streams2 = may && !streams && s16::geometry_s2(l.g.s16s2, l.c, d, c.form == kBackward);   // stride (1,2,2)
+        if (c.form == kForward) {
+            if (streams) take(kStream16Fwd, l);
+            else if (streams2) take(kStream16S2Fwd, l);
+            else generic(kGen16Fwd, c.quantize, d.Ho * d.Wo, d.To);
+            return pl;
+        }
+        if (streams || streams2) {
+            const int bands = streams ? l.g.s16.bands : l.g.s16s2.bands;
+            take(streams ? kStream16Bwd : kStream16S2Bwd, l);
+            if (c.gshift) pl.P = d.N * bands;
         } else {
             if (c.gx) generic(kGen16BwdX, c.quantize, d.H * d.W, d.T);
             if (c.gshift) {

@@ -185,7 +185,8 @@ class RubiksShift3D16Func(torch.autograd.Function):
 
 def _native16(x, shift, stride, padding, quantize):
     """True when the 16-bit kernels take this call: bf16 / f16 activations next to an fp32 shift, RK_SHIFT3D_16 on, and a
-    configuration of the streaming 16-bit family (rk3d_sf32_streams) -- the ones measured faster than the cast path."""
+    configuration of one of the streaming 16-bit families, stride 1 or stride (1,2,2) (rk3d_sf32_streams) -- the ones
+    measured faster than the cast path."""
     if shift.dtype != torch.float32 or not x.is_cuda or not config.switches().shift3d_16:
         return False
     if x.numel() == 0:
