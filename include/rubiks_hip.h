@@ -707,6 +707,44 @@ int rk_se_dgate_f32(const float* dy, const float* x, float* dgate, int F, int C,
 int rk_se_scale_add_f32(const float* x, const float* gate, const float* add, float add_scale, float* y, int F, int C, int P,
                         rk_stream_t stream);
 
+/* ---- the optimizer step of a whole network in one launch (rk_optim.hip; rubiksnet_amd/optim.py) ----------------
+ * fp32 parameters, gradients and state.  jobs: device array of n 48-byte records, 8-byte aligned,
+ *   {float* p; const float* g (float* with zero_grads); float* s0; float* s1; int64 numel; int32 chunk0; int32 group_flags}
+ * one per tensor.  s0 = momentum buffer (SGD; NULL when the group's momentum is 0) or exp_avg (Adam), s1 = exp_avg_sq (Adam).
+ * A tensor is cut into chunks of RK_OPTIM_CHUNK elements, the last one short; chunk0 = the chunks of all tensors before
+ * it (rk_debug_optim_chunks computes the partition: no device call); `chunks` = the total.  group_flags: bits 0..2 the
+ * hyper-parameter group, bit 8 (SGD) this tensor's momentum buffer is uninitialised: it receives g' instead of
+ * momentum buf + (1 - dampening) g', torch's first step.  A workgroup owns one chunk and finds its record by binary search over
+ * chunk0.  16-byte accesses where p, g and the state are all 16-byte aligned, dword accesses for the tail and for any
+ * other tensor; numel 0 is allowed (no chunk).  The table is device data the launcher cannot check.
+ * hyper: HOST array of ngroups records; it travels by value in the kernel arguments (an lr schedule needs no upload);
+ * more than RK_OPTIM_MAX_GROUPS: RK_ERR_UNSUPPORTED, nothing launched.  Every product and sum rounds separately in fp32:
+ *   SGD (torch.optim.SGD):    g' = coef g + wd p;  buf = g' (first) or momentum buf + (1 - dampening) g';
+ *                             p -= lr buf, nesterov: p -= lr (g' + momentum buf);  momentum 0: p -= lr g'
+ *   Adam (torch.optim.Adam, L2 decay): g' = coef g + wd p;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g' g';
+ *                             p -= (lr / bc1) m / (sqrt(v) / bc2_sqrt + eps)     bc1 = 1 - beta1^t, bc2_sqrt = sqrt(1 - beta2^t)
+ * Clipping by the global L2 norm (torch.nn.utils.clip_grad_norm_): rk_optim_sqnorm_many_f32 writes one fp64 sum of g^2 per
+ * chunk into `partials` (rk_optim_sqnorm_workspace_bytes of it); the step launch given partials != NULL has EVERY
+ * workgroup add the npartials values up in one fixed order (fp64), coef = min(1, max_norm / (norm + 1e-6)), and workgroup 0
+ * stores the norm to norm_out (fp32, may be NULL).  Two plain launches on one stream: no hand-off inside a launch, no
+ * atomics; bitwise reproducible.  partials == NULL: coef = 1.  zero_grads != 0: g is overwritten with 0 once read.
+ * No allocation, no synchronisation, no device call besides the launch. */
+#define RK_OPTIM_CHUNK 4096
+#define RK_OPTIM_MAX_GROUPS 8
+typedef struct { float lr, weight_decay, momentum, one_minus_dampening; int nesterov; } rk_optim_sgd_hyper;
+typedef struct { float step_size, weight_decay, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, bc2_sqrt; } rk_optim_adam_hyper;
+/* out[0] = RK_OPTIM_CHUNK, out[1] = chunks in all, out[2 + i] = chunk0 of tensor i (n + 2 ints).  RK_ERR_BAD_DIMS for a
+ * negative numel or more than 2^31 - 1 chunks. */
+int rk_debug_optim_chunks(const long long* numels, int n, int* out);
+size_t rk_optim_sqnorm_workspace_bytes(int chunks);
+int rk_optim_sqnorm_many_f32(const void* jobs, int n, int chunks, double* partials, rk_stream_t stream);
+int rk_optim_sgd_many_f32(const void* jobs, int n, int chunks, const rk_optim_sgd_hyper* hyper, int ngroups,
+                          const double* partials, int npartials, float max_norm, float* norm_out, int zero_grads,
+                          rk_stream_t stream);
+int rk_optim_adam_many_f32(const void* jobs, int n, int chunks, const rk_optim_adam_hyper* hyper, int ngroups,
+                           const double* partials, int npartials, float max_norm, float* norm_out, int zero_grads,
+                           rk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,11 +9,12 @@ reduction that gave up (its outputs are NaN) as a RubiksHipError.
 from . import shiftlib  # noqa: F401
 from . import augment  # noqa: F401
 from . import fin_status  # noqa: F401
+from . import optim  # noqa: F401
 from .attention_shift import AttentionShift
 from .backbone import RubiksNetBackbone
 from .models import RubiksNet
 from .shiftlib import RubiksShift2D, RubiksShift3D, RubiksShiftBase
 
 __all__ = ["RubiksNet", "RubiksNetBackbone", "AttentionShift", "RubiksShift2D", "RubiksShift3D",
-           "RubiksShiftBase", "shiftlib", "augment", "fin_status"]
+           "RubiksShiftBase", "shiftlib", "augment", "fin_status", "optim"]
 __version__ = "0.1.0"

@@ -143,6 +143,13 @@ SIGNATURES["rk_se_mlp_forward_f32"] = (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p])
 SIGNATURES["rk_se_mlp_backward_f32"] = (_i, [_p] * 11 + [_i, _i, _i, _p])
 SIGNATURES["rk_se_dgate_f32"] = (_i, [_p, _p, _p, _i, _i, _i, _p])
 SIGNATURES["rk_se_scale_add_f32"] = (_i, [_p, _p, _p, ctypes.c_float, _p, _i, _i, _i, _p])
+# the one-launch optimizer step (rk_optim.hip): jobs, n, chunks, host hyper-parameter records, groups, partials, count,
+# max_norm, norm_out, zero_grads, stream
+SIGNATURES["rk_debug_optim_chunks"] = (_i, [_p, _i, _p])
+SIGNATURES["rk_optim_sqnorm_workspace_bytes"] = (_sz, [_i])
+SIGNATURES["rk_optim_sqnorm_many_f32"] = (_i, [_p, _i, _i, _p, _p])
+SIGNATURES["rk_optim_sgd_many_f32"] = (_i, [_p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p])
+SIGNATURES["rk_optim_adam_many_f32"] = (_i, [_p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p])
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw

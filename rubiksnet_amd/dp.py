@@ -106,14 +106,24 @@ def wrap_ddp(model, env, bucket_cap_mb=25, force=False):
     return nn.parallel.DistributedDataParallel(model, **kwargs)
 
 
-def make_optimizer(model, lr=0.01, lr_shift_mult=0.01, kind="adam", momentum=0.9, weight_decay=0.0):
+def make_optimizer(model, lr=0.01, lr_shift_mult=0.01, kind="adam", momentum=0.9, weight_decay=0.0, max_grad_norm=None):
     """Two groups as in scripts/example_finetune.py:49-64: parameters whose name ends with
-    'shift' train at lr * lr_shift_mult."""
+    'shift' train at lr * lr_shift_mult.  kind "hip_sgd" / "hip_adam": the same two groups and rules as "sgd" / "adam" in
+    rubiksnet_amd.optim's one-launch step (the shift group through its `lr_mult` key), optionally with clipping by the
+    global gradient norm (`max_grad_norm`, those two kinds only)."""
     shift_params, regular = [], []
     for name, p in model.named_parameters():
         if not p.requires_grad:
             continue
         (shift_params if name.endswith("shift") else regular).append(p)
+    if kind in ("hip_sgd", "hip_adam"):
+        from . import optim
+        groups = [{"params": shift_params, "lr_mult": lr_shift_mult}, {"params": regular}]
+        if kind == "hip_sgd":
+            return optim.RubiksSGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        return optim.RubiksAdam(groups, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    if max_grad_norm is not None:
+        raise ValueError("max_grad_norm needs kind='hip_sgd' or 'hip_adam' (torch's optimizers do not clip)")
     groups = [{"params": shift_params, "lr": lr * lr_shift_mult}, {"params": regular}]
     if kind == "adam":
         # one fused multi-tensor launch per parameter group instead of ~20 foreach kernels per step (RubiksNet-Large: 43
