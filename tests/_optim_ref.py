@@ -1,4 +1,5 @@
-"""fp64 reference and error bounds for the optimizer tests (tests/test_optim.py, tests/test_optim_gpu.py).
+"""fp64 reference and error bounds for the optimizer tests (tests/test_optim.py, tests/test_optim_gpu.py and the lifecycle
+timelines of tests/_optim_timeline.py).
 
 The reference is the update rule evaluated in fp64 (numpy) from the same fp32 inputs.  With u = 2^-24 the unit roundoff and
 S the sum of the absolute values of the terms of an updated quantity, the accepted error is 8 u S elementwise: the rule has
@@ -37,8 +38,12 @@ def global_norm(grads):
 
 
 def clip_coef(norm, max_norm):
-    """torch.nn.utils.clip_grad_norm_'s coefficient; 1 without clipping."""
-    return 1.0 if max_norm is None else min(1.0, max_norm / (norm + 1e-6))
+    """torch.nn.utils.clip_grad_norm_'s coefficient; 1 without clipping.  A NaN norm gives a NaN coefficient, as there (and
+    as the kernel and the torch-op path do): Python's min(1.0, nan) would be 1.0."""
+    if max_norm is None:
+        return 1.0
+    c = max_norm / (norm + 1e-6)
+    return c if c != c else min(1.0, c)
 
 
 def sgd_stage(p, g, buf, p_out, buf_out, lr, wd, momentum, dampening, nesterov, coef=1.0):
@@ -92,6 +97,23 @@ def ratio(out, ref, bound):
     return float(r.max())
 
 
+def ratio_nonfinite(out, ref, bound):
+    """ratio() for steps fed non-finite gradients.  Wherever the output or the reference is not finite the two must agree
+    exactly -- NaN with NaN, an infinity with the infinity of the same sign -- or the ratio is inf; every other position goes
+    through ratio() with its bound, which must be finite there.  With finite data throughout this is ratio()."""
+    out = f64(out)
+    if out.size == 0:
+        return 0.0
+    bound = np.broadcast_to(bound, out.shape)
+    nf = ~(np.isfinite(out) & np.isfinite(ref))
+    with np.errstate(invalid="ignore"):
+        same = (np.isnan(out) & np.isnan(ref)) | (np.isinf(out) & (out == ref))
+    fin = ~nf
+    if (nf & ~same).any() or not np.isfinite(bound[fin]).all():
+        return float("inf")
+    return ratio(out[fin], ref[fin], bound[fin])
+
+
 class Recorder:
     """Snapshots the fp32 inputs of an optimizer step and checks what the step stored against the staged reference.
     kind: "sgd" | "adam"; the hyper-parameters are read from the optimizer's groups at check time (lr may change)."""
@@ -128,23 +150,25 @@ class Recorder:
         return adam_stage(b["p"], b["g"], b["exp_avg"], b["exp_avg_sq"], p, st["exp_avg"], st["exp_avg_sq"], lr, wd,
                           tuple(float(x) for x in group["betas"]), float(group["eps"]), b["t"] + 1, coef)
 
-    def check(self, params, snap, coef=1.0, scale=1.0):
-        """Asserts every stored quantity within `scale` x its bound; keeps the worst ratio per quantity."""
+    def check(self, params, snap, coef=1.0, scale=1.0, nonfinite=False):
+        """Asserts every stored quantity within `scale` x its bound; keeps the worst ratio per quantity.  nonfinite: the
+        step was fed NaN / inf on purpose -- those positions must match the reference's exactly (ratio_nonfinite)."""
         for p, b in zip(params, snap):
             st = self.opt.state.get(p, {})
             for name, (ref, bound) in self.stages(p, b, coef).items():
                 out = p if name == "p" else st[name]
-                r = ratio(out, ref, bound)
+                r = (ratio_nonfinite if nonfinite else ratio)(out, ref, bound)
                 self.worst[name] = max(self.worst.get(name, 0.0), r)
                 assert r <= scale, "%s of a tensor of %d elements: error %.3g x its bound" % (name, b["p"].size, r)
         return self.worst
 
 
-def compare(rec_a, params_a, snap_a, rec_b, params_b, snap_b, coef_a=1.0, coef_b=1.0):
+def compare(rec_a, params_a, snap_a, rec_b, params_b, snap_b, coef_a=1.0, coef_b=1.0, nonfinite=False):
     """Two implementations of one rule stepped from the same fp32 inputs: each stored quantity of A within
     bound_A + bound_B + |ref_A - ref_B| of B's -- twice the bound for buf / m / v, whose reference depends on the inputs alone,
     and for the parameter the same plus the distance of the two staged references (each parameter is held to the reference
-    formed from its own buf / m / v).  Returns the worst ratio."""
+    formed from its own buf / m / v).  nonfinite: as in Recorder.check, B's values standing for the reference.  Returns the
+    worst ratio."""
     worst = 0.0
     for pa, ba, pb, bb in zip(params_a, snap_a, params_b, snap_b):
         sa, sb = rec_a.stages(pa, ba, coef_a), rec_b.stages(pb, bb, coef_b)
@@ -153,7 +177,7 @@ def compare(rec_a, params_a, snap_a, rec_b, params_b, snap_b, coef_a=1.0, coef_b
             oa = pa if name == "p" else rec_a.opt.state[pa][name]
             ob = pb if name == "p" else rec_b.opt.state[pb][name]
             tol = sa[name][1] + sb[name][1] + np.abs(sa[name][0] - sb[name][0])
-            r = ratio(oa, f64(ob), tol)
+            r = (ratio_nonfinite if nonfinite else ratio)(oa, f64(ob), tol)
             worst = max(worst, r)
             assert r <= 1.0, "%s: the two implementations differ by %.3g x the allowed distance" % (name, r)
     return worst
