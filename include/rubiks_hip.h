@@ -745,6 +745,40 @@ int rk_optim_adam_many_f32(const void* jobs, int n, int chunks, const rk_optim_a
                            const double* partials, int npartials, float max_norm, float* norm_out, int zero_grads,
                            rk_stream_t stream);
 
+/* ---- streaming metrics: loss, top-k and per-class accuracy accumulated on the device (rk_metrics.hip; ---------------
+ * rubiksnet_amd/metrics.py).  One launch scores `videos` videos: logits [videos * views, classes] row-major contiguous
+ * (row b * views + v = view v of video b), labels [videos] int64.  In fp32:
+ *   z[k] = (sum over v ascending of x[b, v, k]) / views;   pred = the lowest index among the maxima of z;
+ *   rank = #{j : z[j] > z[y]} + #{j < y : z[j] == z[y]}    (a hit at k when rank < k; rank 0 <=> pred == y);
+ *   loss = (max + logf(sum expf(z - max))) - z[y], clamped to [0, 2^20].
+ * A label outside [0, classes) adds 1 to bad_labels and nothing else (it is checked before it indexes anything).  A video
+ * with a NaN or an infinity in z adds 1 to videos, nonfinite and its label's count: a miss at every k, nothing to the loss
+ * sum or the confusion matrix.  state: int64 words, 8-byte aligned, rk_metrics_state_bytes of them, zeroed by the caller:
+ *   [0] videos  [1] loss sum in units of 2^-32 (llrint(loss * 2^32) per video)  [2] nonfinite  [3] bad_labels
+ *   [4..8) hits per top-k slot   [8..8+K) videos per label   [8+K..8+2K) top-1 hits per label
+ *   [8+2K..8+2K+K*K) confusion[label][pred], only when confusion != 0
+ * Words are added with 64-bit integer atomics only: the state is bit-identical from run to run, and the states of several
+ * ranks merge with one integer sum.  No workgroup waits on another.  ntopk values of k (k0.. in slot order, each >= 1; the
+ * rest ignored) travel by value.  Per-video outputs, each may be NULL: consensus f32 [videos, classes], pred int32, rank
+ * int32, loss f32 [videos]; a bad label or a non-finite video stores rank -1 and loss NaN, a non-finite one pred -1.
+ * Returns RK_ERR_NULL_POINTER (logits, labels, state), RK_ERR_BAD_DIMS (a dimension <= 0, videos * views * classes >= 2^31,
+ * a k < 1, ntopk < 0, misaligned state), RK_ERR_UNSUPPORTED (views > 64, classes > 65536, ntopk > 4) before anything
+ * touches a device.  No allocation, no synchronisation, no device call besides the launch. */
+#define RK_METRICS_MAX_TOPK 4
+#define RK_METRICS_MAX_VIEWS 64
+#define RK_METRICS_MAX_CLASSES 65536
+#define RK_METRICS_HEAD_WORDS 8
+size_t rk_metrics_state_bytes(int classes, int confusion); /* 0 for classes outside [1, 65536] */
+int rk_metrics_update_f32(const float* logits, const long long* labels, long long* state, int videos, int views, int classes,
+                          int confusion, int ntopk, int k0, int k1, int k2, int k3, float* consensus, int* pred, int* rank,
+                          float* loss, rk_stream_t stream);
+int rk_metrics_update_bf16(const void* logits, const long long* labels, long long* state, int videos, int views, int classes,
+                           int confusion, int ntopk, int k0, int k1, int k2, int k3, float* consensus, int* pred, int* rank,
+                           float* loss, rk_stream_t stream);
+int rk_metrics_update_f16(const void* logits, const long long* labels, long long* state, int videos, int views, int classes,
+                          int confusion, int ntopk, int k0, int k1, int k2, int k3, float* consensus, int* pred, int* rank,
+                          float* loss, rk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

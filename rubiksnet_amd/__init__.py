@@ -4,17 +4,20 @@ Public surface mirrors the reference package `rubiksnet`: `shiftlib` (RubiksShif
 RubiksShift3D, RubiksShiftBase + functionals), `AttentionShift`, `RubiksNetBackbone`,
 `RubiksNet`.  All device work goes through librubiks_hip.so (include/rubiks_hip.h);
 importing the package does not load it, calling an operator does.  `fin_status` reports an in-launch
-reduction that gave up (its outputs are NaN) as a RubiksHipError.
+reduction that gave up (its outputs are NaN) as a RubiksHipError; `metrics.StreamMeter` accumulates loss, top-k and per-class
+accuracy on the device.
 """
 from . import shiftlib  # noqa: F401
 from . import augment  # noqa: F401
 from . import fin_status  # noqa: F401
 from . import optim  # noqa: F401
+from . import metrics  # noqa: F401
 from .attention_shift import AttentionShift
 from .backbone import RubiksNetBackbone
+from .metrics import StreamMeter
 from .models import RubiksNet
 from .shiftlib import RubiksShift2D, RubiksShift3D, RubiksShiftBase
 
 __all__ = ["RubiksNet", "RubiksNetBackbone", "AttentionShift", "RubiksShift2D", "RubiksShift3D",
-           "RubiksShiftBase", "shiftlib", "augment", "fin_status", "optim"]
+           "RubiksShiftBase", "shiftlib", "augment", "fin_status", "optim", "metrics", "StreamMeter"]
 __version__ = "0.1.0"

@@ -150,6 +150,11 @@ SIGNATURES["rk_optim_sqnorm_workspace_bytes"] = (_sz, [_i])
 SIGNATURES["rk_optim_sqnorm_many_f32"] = (_i, [_p, _i, _i, _p, _p])
 SIGNATURES["rk_optim_sgd_many_f32"] = (_i, [_p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p])
 SIGNATURES["rk_optim_adam_many_f32"] = (_i, [_p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p])
+# the streaming metrics launch (rk_metrics.hip): logits, labels, state, videos, views, classes, confusion, ntopk, k0..k3,
+# consensus, pred, rank, loss (each may be NULL), stream
+SIGNATURES["rk_metrics_state_bytes"] = (_sz, [_i, _i])
+for _sfx in ("f32", "bf16", "f16"):
+    SIGNATURES["rk_metrics_update_" + _sfx] = (_i, [_p, _p, _p] + [_i] * 9 + [_p] * 5)
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw

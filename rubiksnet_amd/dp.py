@@ -138,10 +138,11 @@ def make_optimizer(model, lr=0.01, lr_shift_mult=0.01, kind="adam", momentum=0.9
     return torch.optim.SGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay)
 
 
-def train_step(model, optimizer, clips, labels, criterion=None):
+def train_step(model, optimizer, clips, labels, criterion=None, meter=None):
     """zero_grad -> forward -> CE -> backward (+ DDP all-reduce) -> step
     (scripts/example_finetune.py:85-97).  Raises RubiksHipError when an in-launch finalizer of this or the previous step gave
-    up (fin_status.poll: no host wait; every rank looks at its own device only)."""
+    up (fin_status.poll: no host wait; every rank looks at its own device only).  meter: a metrics.StreamMeter that scores the
+    step's logits against `labels` on the device (one launch, no host wait; read it with meter.result() when the epoch ends)."""
     criterion = criterion or nn.functional.cross_entropy
     optimizer.zero_grad(set_to_none=True)
     bf16_step = (clips.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
@@ -152,6 +153,8 @@ def train_step(model, optimizer, clips, labels, criterion=None):
             out = model(clips)
         loss = criterion(out, labels)
         loss.backward()
+    if meter is not None:
+        meter.update(out.detach(), labels)
     optimizer.step()
     fin_status.poll()
     return loss

@@ -7,7 +7,7 @@ are averaged over the views of a video, and top-1 / top-5 precision is accumulat
 """
 import torch
 
-__all__ = ["accuracy", "fold_views", "video_logits", "AverageMeter", "evaluate"]
+__all__ = ["accuracy", "fold_views", "video_logits", "AverageMeter", "evaluate", "evaluate_streaming"]
 
 
 def accuracy(output, target, topk=(1,)):
@@ -70,3 +70,34 @@ def evaluate(model, batches, n_frames=8, views=1):
     return {"top1": top1.avg, "top5": top5.avg, "videos": top1.count,
             "logits": torch.cat(all_logits) if all_logits else torch.empty(0),
             "labels": torch.cat(all_labels) if all_labels else torch.empty(0, dtype=torch.long)}
+
+
+@torch.no_grad()
+def evaluate_streaming(model, batches, n_frames=8, views=1, meter=None, keep_logits=False):
+    """evaluate()'s loop with no host wait inside it: every batch's logits are scored on the device by a
+    metrics.StreamMeter (one launch: consensus over the views, rank of the label, cross-entropy, per-class counts, confusion
+    matrix) and the state is read once, after the last batch.  Returns meter.result() -- videos, loss, top1, top5 (the k of
+    the meter), per_class_acc, mean_class_acc, confusion, nonfinite, bad_labels: the confusion matrix and per-class
+    accuracy are what the reference's script ends with (test_models.py:198-205).  meter: a StreamMeter of `views` views to
+    accumulate into (several loaders, or ranks to all_reduce before reading); default a new one, topk (1, 5).
+    keep_logits: also "logits" [N, K] fp32 and "labels" [N], kept on the device batch by batch and copied once at the end."""
+    from .metrics import StreamMeter
+    model.eval()
+    kept_logits, kept_labels = [], []
+    for data, label in batches:
+        dev = next(model.parameters()).device
+        out = model(fold_views(data.to(dev, non_blocking=True), n_frames, views))
+        if meter is None:
+            meter = StreamMeter(out.size(1), topk=(1, 5), views=views)
+        label = label.to(out.device, non_blocking=True)
+        got = meter.update(out, label, outputs=("consensus",) if keep_logits else ())
+        if keep_logits:
+            kept_logits.append(got["consensus"])
+            kept_labels.append(label)
+    if meter is None:
+        raise ValueError("no batches and no meter: the number of classes is unknown")
+    result = meter.result()
+    if keep_logits:
+        result["logits"] = torch.cat(kept_logits).cpu() if kept_logits else torch.empty(0)
+        result["labels"] = torch.cat(kept_labels).cpu() if kept_labels else torch.empty(0, dtype=torch.long)
+    return result
