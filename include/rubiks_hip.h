@@ -744,6 +744,30 @@ int rk_optim_sgd_many_f32(const void* jobs, int n, int chunks, const rk_optim_sg
 int rk_optim_adam_many_f32(const void* jobs, int n, int chunks, const rk_optim_adam_hyper* hyper, int ngroups,
                            const double* partials, int npartials, float max_norm, float* norm_out, int zero_grads,
                            rk_stream_t stream);
+/* The extended step: the same table, partials, norm_out and zero_grads as above, and opt-in
+ *   rule: RK_OPTIM_RULE_SGD / _ADAM (hyper: HOST array of rk_optim_sgd_hyper / rk_optim_adam_hyper, the rules above) or
+ *     RK_OPTIM_RULE_ADAMW (torch.optim.AdamW; rk_optim_adamw_hyper): p1 = decay_factor p with decay_factor = 1 - lr wd formed
+ *     by the caller in double and rounded once; g' = coef g (no L2 term); m, v as Adam;
+ *     p = p1 - (lr / bc1) m / (sqrt(v) / bc2_sqrt + eps).  Another rule: RK_ERR_UNSUPPORTED.
+ *   ema: NULL, or a device array of n pointers (8-byte aligned) parallel to the table: the fp32 EMA shadow of tensor i, of
+ *     numel elements, or NULL for a tensor without one.  After the rule has produced the new p:
+ *     e = ema_decay e + ema_one_minus_decay p_new (two products, one sum, each rounded).  The two factors apply to the whole
+ *     launch and travel by value: a warm-up schedule uploads nothing.  16-byte accesses where p, g, the states AND e are
+ *     16-byte aligned, dword accesses otherwise.
+ *   guard != 0: needs partials (RK_ERR_WORKSPACE without, nothing launched) and skipped, an 8-byte aligned device int64.
+ *     When the fp64 sum of the partials is NaN or an infinity, NO workgroup writes p, a state or a shadow (every workgroup
+ *     forms the same sum bit for bit: no hand-off, no polling, no atomics); zero_grads still zeroes the gradients; thread 0
+ *     of workgroup 0 stores the non-finite norm to norm_out and adds 1 to *skipped with a plain load and store (one writer
+ *     per launch, launches ordered by the stream).  A finite sum -- gradients of 1e25 included, whose squares overflow fp32
+ *     only -- is an ordinary step.  Guarding without clipping: max_norm = +inf gives coef = 1.
+ * Everything is validated before the launch; no allocation, no synchronisation, no device call besides the launch. */
+#define RK_OPTIM_RULE_SGD 0
+#define RK_OPTIM_RULE_ADAM 1
+#define RK_OPTIM_RULE_ADAMW 2
+typedef struct { float step_size, decay_factor, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, bc2_sqrt; } rk_optim_adamw_hyper;
+int rk_optim_step_ext_f32(int rule, const void* jobs, int n, int chunks, const void* hyper, int ngroups, const double* partials,
+                          int npartials, float max_norm, float* norm_out, int zero_grads, const void* ema, float ema_decay,
+                          float ema_one_minus_decay, int guard, long long* skipped, rk_stream_t stream);
 
 /* ---- streaming metrics: loss, top-k and per-class accuracy accumulated on the device (rk_metrics.hip; ---------------
  * rubiksnet_amd/metrics.py).  One launch scores `videos` videos: logits [videos * views, classes] row-major contiguous

@@ -150,6 +150,9 @@ SIGNATURES["rk_optim_sqnorm_workspace_bytes"] = (_sz, [_i])
 SIGNATURES["rk_optim_sqnorm_many_f32"] = (_i, [_p, _i, _i, _p, _p])
 SIGNATURES["rk_optim_sgd_many_f32"] = (_i, [_p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p])
 SIGNATURES["rk_optim_adam_many_f32"] = (_i, [_p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p])
+# the extended step: rule, then as above up to zero_grads, then ema pointers, ema_decay, 1 - ema_decay, guard, skipped, stream
+SIGNATURES["rk_optim_step_ext_f32"] = (_i, [_i, _p, _i, _i, _p, _i, _p, _i, ctypes.c_float, _p, _i, _p, ctypes.c_float,
+                                            ctypes.c_float, _i, _p, _p])
 # the streaming metrics launch (rk_metrics.hip): logits, labels, state, videos, views, classes, confusion, ntopk, k0..k3,
 # consensus, pred, rank, loss (each may be NULL), stream
 SIGNATURES["rk_metrics_state_bytes"] = (_sz, [_i, _i])

@@ -106,24 +106,29 @@ def wrap_ddp(model, env, bucket_cap_mb=25, force=False):
     return nn.parallel.DistributedDataParallel(model, **kwargs)
 
 
-def make_optimizer(model, lr=0.01, lr_shift_mult=0.01, kind="adam", momentum=0.9, weight_decay=0.0, max_grad_norm=None):
+def make_optimizer(model, lr=0.01, lr_shift_mult=0.01, kind="adam", momentum=0.9, weight_decay=0.0, max_grad_norm=None,
+                   ema_decay=None, skip_nonfinite=False):
     """Two groups as in scripts/example_finetune.py:49-64: parameters whose name ends with
     'shift' train at lr * lr_shift_mult.  kind "hip_sgd" / "hip_adam": the same two groups and rules as "sgd" / "adam" in
-    rubiksnet_amd.optim's one-launch step (the shift group through its `lr_mult` key), optionally with clipping by the
-    global gradient norm (`max_grad_norm`, those two kinds only)."""
+    rubiksnet_amd.optim's one-launch step (the shift group through its `lr_mult` key), "hip_adamw": torch.optim.AdamW's rule
+    there; optionally with clipping by the global gradient norm (`max_grad_norm`), EMA weights for evaluation (`ema_decay`)
+    and a guard that skips a step whose gradients are not finite (`skip_nonfinite`) -- the hip_* kinds only."""
     shift_params, regular = [], []
     for name, p in model.named_parameters():
         if not p.requires_grad:
             continue
         (shift_params if name.endswith("shift") else regular).append(p)
-    if kind in ("hip_sgd", "hip_adam"):
+    if kind in ("hip_sgd", "hip_adam", "hip_adamw"):
         from . import optim
         groups = [{"params": shift_params, "lr_mult": lr_shift_mult}, {"params": regular}]
+        extra = dict(max_grad_norm=max_grad_norm, ema_decay=ema_decay, skip_nonfinite=skip_nonfinite)
         if kind == "hip_sgd":
-            return optim.RubiksSGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
-        return optim.RubiksAdam(groups, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+            return optim.RubiksSGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, **extra)
+        return (optim.RubiksAdam if kind == "hip_adam" else optim.RubiksAdamW)(groups, lr=lr, weight_decay=weight_decay, **extra)
     if max_grad_norm is not None:
         raise ValueError("max_grad_norm needs kind='hip_sgd' or 'hip_adam' (torch's optimizers do not clip)")
+    if ema_decay is not None or skip_nonfinite:
+        raise ValueError("ema_decay and skip_nonfinite need a hip_* kind (rubiksnet_amd.optim's one-launch step)")
     groups = [{"params": shift_params, "lr": lr * lr_shift_mult}, {"params": regular}]
     if kind == "adam":
         # one fused multi-tensor launch per parameter group instead of ~20 foreach kernels per step (RubiksNet-Large: 43
