@@ -38,8 +38,9 @@
  *     on the CURRENT device of the calling thread (hipGetDevice); the Python layer sets it from the tensors' device.
  *   - environment switches, each read once per process:
  *       RK_SHIFT_KERNELS = auto | column | generic selects which kernel families the shift operators may use
- *         (rk_common.hpp; 3-D: rk3d_plan.hpp plan3d::plan, rk_debug_3d_plan shows the choice; every family is bit-identical
- *         for y and d(x), tests/test_fallback_paths_gpu.py);
+ *         (rk_common.hpp; 3-D: rk3d_plan.hpp plan3d::plan, rk_debug_3d_plan shows the choice; 2-D: rk2d_plan.hpp plan2d::plan,
+ *         rk_debug_2d_plan, held by tests/test_plan2d.py; every family is bit-identical for y and d(x),
+ *         tests/test_fallback_paths_gpu.py);
  *         RK_FORCE_GENERIC=1 is the older spelling of `generic`;
  *       RK_PW2 = 1 | 0 | 2, RK_PW3 = 1 | 0, RK_PW4 = 1 | 0 | 2: the fp32 1x1 kernel generations (rk_pw.hip: plan_gemm;
  *         rk_debug_pw_gemm_plan shows the choice);
@@ -126,6 +127,16 @@ int rk_debug_pw_wgrad_plan(int F, int K, int M, int P, int pw2);
 int rk_debug_3d_plan(int form, int elem_size, int N, int T, int C, int H, int W, int sT, int sH, int sW, int pT, int pH, int pW,
                      int quantize, int want_gx, int want_gshift, int two_phase, int aligned, int shift_kernels, int slab14,
                      int* out);
+/* the RubiksShift2D kernel choice (rk2d_plan.hpp: plan2d::plan) with explicit switches and alignments, no device call.
+ * form: 0 forward, 1 backward (want_gshift: enable_shift_grad), 2 rk2d_forward_bn_*, 3 rk2d_backward_bn_*; elem_size 4 / 8 / 2
+ * (f16 / bf16 activations, either shift type); aligned: two bits per operand from bit 0 -- x / z, y (forward) or gy, gx / dz, the
+ * BatchNorm pack -- 2: a multiple of 16 bytes, 1: of 8, 0: neither; shift_kernels: 0 auto, 1 column, 2 generic
+ * (RK_SHIFT_KERNELS); cus: compute units of the device.  Returns the status the call would have as far as it does not depend
+ * on pointers.  out[36]: launches, P (partials per channel and sum: the workspace holds [C][2 or 4][P]), whether k2d_finalize /
+ * k2d_finalize_bn follows as a launch of its own, then per launch (3 x 11): family (the enum of rk2d_plan.hpp), negate, bn,
+ * rounds, M, single, vec, quant, grid, block, dynamic LDS bytes. */
+int rk_debug_2d_plan(int form, int elem_size, int N, int C, int H, int W, int sH, int sW, int pH, int pW, int quantize,
+                     int want_gshift, int aligned, int shift_kernels, int cus, int* out);
 
 /* ------------------------------------------------------------------------- 3D
  * Replaces rubiks_shift_3d_forward<T>  (cuda_src/rubiks.cpp:181-253) + functor

@@ -32,6 +32,7 @@ SIGNATURES = {
     "rk_debug_pw_gemm_plan": (_i, [_i] * 14 + [_p]),
     "rk_debug_pw_wgrad_plan": (_i, [_i] * 5),
     "rk_debug_3d_plan": (_i, [_i] * 20 + [_p]),
+    "rk_debug_2d_plan": (_i, [_i] * 15 + [_p]),
     "rk3d_debug_finalize_only_f32": (_i, [_p, _sz, _i, _i, _p, _i, ctypes.c_float, _p]),
     "rk_fin_status_register": (_i, [_p]),
     "rk3d_debug_finalize_only_status_f32": (_i, [_p, _sz, _i, _i, _p, _i, ctypes.c_float, _p, _p]),

@@ -8,16 +8,11 @@
 // f16 / bf16 tensors are computed in fp32 and rounded once on store; only the quantize
 // position arithmetic is done in the storage type, because it decides WHICH element is
 // gathered (the reference instantiates the whole kernel at c10::Half).
-#include <type_traits>
-#include "rk2d_generic.hpp"
-#include "rk2d_dma.hpp"
-#include "rk2d_stage.hpp"
-#include "rk2d_raw16.hpp"
-#include "rk2d_tile.hpp"
-#include "rk2d_column.hpp"
+#include "rk2d_plan.hpp"
 
 using namespace rk;
 using namespace rk::g2d;
+using namespace rk::plan2d;
 
 namespace {
 
@@ -33,193 +28,146 @@ int make_dims2(Dims2& d, int N, int C, int H, int W, int sH, int sW, int pH, int
     return RK_OK;
 }
 
-void set_group2(Dims2& d, int plane_elems) {
-    d.E = pow2_at_least(plane_elems, kWave, kBlock);
-    d.logE = (d.E == 64) ? 6 : (d.E == 128 ? 7 : 8);
-}
+// the process's RK_SHIFT_KERNELS (rk_common.hpp), read once, and the current device's compute units
+Switches env_switches() { return Switches{shift_kernels(), device_cus()}; }
+// the shape-only answers (workspace sizes, rk2d_bn_fused_shape) make no device call: the CU count moves the frames per wave
+// of the 16-bit 14x14 backward (rk2d_tile.hpp), never eligibility, and the workspace bound is taken at the least frames per wave
+Switches shape_switches() { return Switches{shift_kernels(), 256}; }
+// what plan2d::Call::align holds for an operand
+int al(const void* p) { return ((uintptr_t)p & 15) == 0 ? 16 : ((uintptr_t)p & 7) == 0 ? 8 : 0; }
 
-// bytes of d(shift) partials: [C][2][P], P = N for the generic kernels
-size_t workspace2(const Dims2& d, size_t elem) {
-    // the smaller group size gives the larger partial count: an upper bound for every storage type
-    int P = dma2d::backward2_partials(d, dma2d::kFramesF32 < dma2d::kFrames16 ? dma2d::kFramesF32 : dma2d::kFrames16);
-    const int Pc = col2d::backward_partials(d), Pr = raw16::backward2_partials(d);
-    P = P > Pc ? P : Pc;
-    P = P > Pr ? P : Pr;
-    const int Pt = tile2d::backward2_partials<float>(d);             // (the same count for every storage type)
-    P = P > Pt ? P : Pt;
-    // the streaming backwards keep their fp32 partials as 16-byte granule pairs (rk_dma.hpp: fin_publish)
-    return (size_t)d.C * 2 * (size_t)(P > d.N ? P : d.N) * 16;
-}
+// the operands of a call, by the names the launchers use.  T: storage type of the activations; S: storage type of the shift
+// table and of d(shift).  S == T is the reference's instantiation (the whole kernel at one scalar type,
+// rubiks2d_kernels.cu:422); S = float next to 16-bit activations keeps the fp32 parameter of an autocast network un-rounded
+// (and returns d(shift) in fp32).
+template <typename T, typename S> struct Ops {
+    const T* x; const S* shift; const T* gy; T* y; T* gx; S* gshift; void* ws;
+    int normalize;
+    const float* ab;              // the BN forward's [2][C]
+    dma2d::BnFuse2 bn;            // the BN backward's pack and outputs
+};
 
-unsigned grid2(const Dims2& d) {
-    const int per_block = kBlock / d.E;
-    return (unsigned)(((long long)d.N * d.C + per_block - 1) / per_block);
-}
-
-// T: storage type of the activations; S: storage type of the shift table and of d(shift).  S == T is the
-// reference's instantiation (the whole kernel at one scalar type, rubiks2d_kernels.cu:422); S = float next to
-// 16-bit activations keeps the fp32 parameter of an autocast network un-rounded (and returns d(shift) in fp32).
+// runs one planned launch
 template <typename T, typename S>
-int forward2(const void* x_, const void* shift_, void* y_, int N, int C, int H, int W, int sH, int sW, int pH,
-             int pW, int quantize, rk_stream_t stream_) {
-    const T* x = (const T*)x_; const S* shift = (const S*)shift_; T* y = (T*)y_;
-    if (!x || !shift || !y) return RK_ERR_NULL_POINTER;
-    Dims2 d;
-    if (int rc = make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    if constexpr (!std::is_same<T, double>::value) {
-        if (!quantize && tile2d::launch_interp2<T, false>(x, shift, y, d, stream)) return launch_status();   // 14x14
+void run(const Launch& l, const Dims2& d, int P, const Ops<T, S>& o, hipStream_t stream) {
+    using CT = typename Compute<T>::type;
+    const Cfg2& c = l.c;
+    const T* src = c.negate ? o.gy : o.x;                              // forward / d(x)-only families
+    T* dst = c.negate ? o.gx : o.y;
+    const dim3 grid(c.grid), block(kBlock);
+    if constexpr (!std::is_same<T, double>::value) {                   // the streaming families; a fused backward's finalizers
+        const bool fused = l.family == kDmaBwd || l.family == kStageBwd || l.family == kRawBwd || l.family == kTileBwd;
+        const dma2d::Fin2<S> fin = fused ? dma2d::make_fin2(o.ws, (int)c.grid - d.C, o.gshift, o.normalize) : dma2d::Fin2<S>{};
+        if (l.family == kTileInterp) return tile2d::launch_interp(c, l.g.tile, src, o.shift, dst, o.ab, stream);
+        if (l.family == kTileBwd) return tile2d::launch_backward(c, l.g.tile, o.gy, o.x, o.shift, o.gx, fin, o.bn, stream);
+        if constexpr (std::is_same<T, float>::value) {
+            if (l.family == kDmaInterp) return dma2d::launch_interp(c, l.g.band, src, o.shift, dst, stream);
+            if (l.family == kDmaBwd) return dma2d::launch_backward(c, l.g.band, d, o.gy, o.x, o.shift, o.gx, fin, stream);
+        } else {
+            if (l.family == kRawInterp) return raw16::launch_interp(c, l.g.band, src, o.shift, dst, o.ab, stream);
+            if (l.family == kRawBwd) return raw16::launch_backward(c, l.g.band, o.gy, o.x, o.shift, o.gx, fin, o.bn, stream);
+            if (l.family == kStageInterp) return stage2d::launch_interp(c, l.g.band, src, o.shift, dst, o.ab, stream);
+            if (l.family == kStageBwd) return stage2d::launch_backward(c, l.g.band, d, o.gy, o.x, o.shift, o.gx, fin, o.bn, stream);
+        }
     }
-    if constexpr (std::is_same<T, float>::value) {
-        if (!quantize && dma2d::launch_interp2<false>(x, shift, y, d, stream)) return launch_status();
-    } else if constexpr (!std::is_same<T, double>::value) {
-        if (!quantize && raw16::launch_interp2<T, false>(x, shift, y, d, stream)) return launch_status();   // W % 8 == 0
-        if (!quantize && stage2d::launch_interp2<T, false>(x, shift, y, d, stream)) return launch_status();
+    switch (l.family) {
+        case kColFwd: return col2d::launch_forward(c, l.g.col, o.x, o.shift, o.y, o.ab, stream);
+        case kColBwd: return col2d::launch_backward(c, l.g.col, o.gy, o.x, o.shift, o.gx, (CT*)o.ws, o.bn.abmi, stream);
+        case kGenFwd:
+            if (c.quant) hipLaunchKernelGGL((k2d_forward<T, S, true>), grid, block, 0, stream, o.x, o.shift, o.y, l.g.gen);
+            else hipLaunchKernelGGL((k2d_forward<T, S, false>), grid, block, 0, stream, o.x, o.shift, o.y, l.g.gen);
+            return;
+        case kGenBwdX:
+            if (c.quant) hipLaunchKernelGGL((k2d_backward_input<T, S, true>), grid, block, 0, stream, o.gy, o.shift, o.gx, l.g.gen);
+            else hipLaunchKernelGGL((k2d_backward_input<T, S, false>), grid, block, 0, stream, o.gy, o.shift, o.gx, l.g.gen);
+            return;
+        case kGenBwdS:
+            hipLaunchKernelGGL((k2d_backward_shift<T, S>), grid, block, 0, stream, o.gy, o.x, o.shift, (CT*)o.ws, l.g.gen);
+            return;
+        case kFinalize:
+            hipLaunchKernelGGL((k2d_finalize<T, S>), grid, dim3(finalize_block(P)), 0, stream, (const CT*)o.ws, o.gshift, d.C, P,
+                               o.normalize);
+            return;
+        case kFinalizeBn:
+            if constexpr (kBnVariant<T, S>)
+                hipLaunchKernelGGL(col2d::k2d_finalize_bn, grid, dim3(finalize_block(P)), 0, stream, (const float*)o.ws, o.gshift,
+                                   o.bn.k12, o.bn.dgamma, o.bn.dbeta, d.C, P, o.normalize, o.bn.inv_count);
+            return;
+        default: return;
     }
-    // small planes only: on larger ones the per-plane kernel below is the faster forward (stride-2 56x56 ->
-    // 28x28: 85 vs 102 us); the column BACKWARD wins everywhere (fused, single-tap)
-    // (16-bit strided layers: the column kernel with 8-byte stores also wins on the large planes, 108 -> 84 us at
-    // [256,108,56,56] bf16; in fp32 it loses there, 84 -> 97 us)
-    if (col2d::supported(quantize) && (d.Ho * d.Wo <= kBlock || (sizeof(T) == 2 && (d.sH > 1 || d.sW > 1)))) {
-        col2d::launch_forward<T>(x, shift, y, d, stream);
-        return launch_status();
-    }
-    set_group2(d, d.Ho * d.Wo);
-    if (quantize)
-        hipLaunchKernelGGL((k2d_forward<T, S, true>), dim3(grid2(d)), dim3(kBlock), 0, stream, x, shift, y, d);
-    else
-        hipLaunchKernelGGL((k2d_forward<T, S, false>), dim3(grid2(d)), dim3(kBlock), 0, stream, x, shift, y, d);
+}
+template <typename T, typename S>
+int run(const Call& c, const Ops<T, S>& o, rk_stream_t stream) {
+    const Plan pl = plan(c, env_switches());
+    if (pl.rc) return pl.rc;
+    for (int i = 0; i < pl.n; ++i) run<T, S>(pl.l[i], c.d, pl.P, o, (hipStream_t)stream);
     return launch_status();
 }
 
 template <typename T, typename S>
-int backward2(const void* gy_, const void* x_, const void* shift_, void* gx_, void* gshift_, int N, int C, int H,
-              int W, int sH, int sW, int pH, int pW, int normalize_grad, int enable_shift_grad, int quantize,
-              void* ws, size_t ws_bytes, rk_stream_t stream_) {
-    using CT = typename Compute<T>::type;
-    const T* gy = (const T*)gy_; const T* x = (const T*)x_; const S* shift = (const S*)shift_;
-    T* gx = (T*)gx_; S* gshift = (S*)gshift_;
+int forward2(const void* x, const void* shift, void* y, int N, int C, int H, int W, int sH, int sW, int pH, int pW, int quantize,
+             rk_stream_t stream) {
+    if (!x || !shift || !y) return RK_ERR_NULL_POINTER;
+    Call c{};
+    if (int rc = make_dims2(c.d, N, C, H, W, sH, sW, pH, pW)) return rc;
+    c.form = kForward; c.elem = (int)sizeof(T); c.quantize = quantize;
+    c.align[kX] = al(x); c.align[kY] = al(y); c.align[kGx] = c.align[kBn] = 16;
+    Ops<T, S> o{};
+    o.x = (const T*)x; o.shift = (const S*)shift; o.y = (T*)y;
+    return run(c, o, stream);
+}
+
+template <typename T, typename S>
+int backward2(const void* gy, const void* x, const void* shift, void* gx, void* gshift, int N, int C, int H, int W, int sH, int sW,
+              int pH, int pW, int normalize_grad, int enable_shift_grad, int quantize, void* ws, size_t ws_bytes,
+              rk_stream_t stream) {
     if (!gy || !shift || !gx) return RK_ERR_NULL_POINTER;
     if (enable_shift_grad && (!x || !gshift)) return RK_ERR_NULL_POINTER;
-    Dims2 d;
-    if (int rc = make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (enable_shift_grad) {
-        if (!ws || ws_bytes < workspace2(d, sizeof(CT))) return RK_ERR_WORKSPACE;
-    }
-    if constexpr (!std::is_same<T, double>::value) {
-        if (!quantize) {                                                                       // 14x14 planes
-            if (!enable_shift_grad) {
-                if (tile2d::launch_interp2<T, true>(gy, shift, gx, d, stream)) return launch_status();
-            } else if (tile2d::launch_backward2<T>(gy, x, shift, gx, gshift, ws, normalize_grad, d, stream)) {
-                return launch_status();
-            }
-        }
-    }
-    if constexpr (std::is_same<T, float>::value) {
-        if (!quantize) {
-            if (!enable_shift_grad) {
-                if (dma2d::launch_interp2<true>(gy, shift, gx, d, stream)) return launch_status();
-            } else if (dma2d::launch_backward2(gy, x, shift, gx, gshift, ws, normalize_grad, d, stream)) {
-                return launch_status();                               // row-sum + K9 happened inside the launch
-            }
-        }
-    } else if constexpr (!std::is_same<T, double>::value) {
-        if (!quantize) {
-            if (!enable_shift_grad) {
-                if (raw16::launch_interp2<T, true>(gy, shift, gx, d, stream)) return launch_status();
-                if (stage2d::launch_interp2<T, true>(gy, shift, gx, d, stream)) return launch_status();
-            } else if (raw16::launch_backward2<T>(gy, x, shift, gx, gshift, ws, normalize_grad, d, stream) ||
-                       stage2d::launch_backward2<T>(gy, x, shift, gx, gshift, ws, normalize_grad, d, stream)) {
-                return launch_status();
-            }
-        }
-    }
-    if (enable_shift_grad && col2d::supported(quantize)) {                // fused d(x) + d(shift), any stride / H x W
-        const int P = col2d::launch_backward<T>(gy, x, shift, gx, (CT*)ws, d, stream);
-        hipLaunchKernelGGL((k2d_finalize<T, S>), dim3(C), dim3(finalize_block(P)), 0, stream, (const CT*)ws, gshift, C, P,
-                           normalize_grad);
-        return launch_status();
-    }
-    if (enable_shift_grad) {                                              // rubiks.cpp:126-149
-        CT* part = (CT*)ws;
-        set_group2(d, d.Ho * d.Wo);
-        hipLaunchKernelGGL((k2d_backward_shift<T, S>), dim3(grid2(d)), dim3(kBlock), 0, stream, gy, x, shift, part, d);
-        hipLaunchKernelGGL((k2d_finalize<T, S>), dim3(C), dim3(finalize_block(N)), 0, stream, (const CT*)part, gshift, C, N,
-                           normalize_grad);
-    }
-    set_group2(d, d.H * d.W);                                             // rubiks.cpp:151-153
-    if (quantize)
-        hipLaunchKernelGGL((k2d_backward_input<T, S, true>), dim3(grid2(d)), dim3(kBlock), 0, stream, gy, shift, gx, d);
-    else
-        hipLaunchKernelGGL((k2d_backward_input<T, S, false>), dim3(grid2(d)), dim3(kBlock), 0, stream, gy, shift, gx, d);
-    return launch_status();
+    Call c{};
+    if (int rc = make_dims2(c.d, N, C, H, W, sH, sW, pH, pW)) return rc;
+    if (enable_shift_grad && (!ws || ws_bytes < workspace_bytes(c.d, shape_switches()))) return RK_ERR_WORKSPACE;
+    c.form = kBackward; c.elem = (int)sizeof(T); c.quantize = quantize; c.gshift = enable_shift_grad;
+    c.align[kX] = al(x); c.align[kY] = al(gy); c.align[kGx] = al(gx); c.align[kBn] = 16;
+    Ops<T, S> o{};
+    o.gy = (const T*)gy; o.x = (const T*)x; o.shift = (const S*)shift; o.gx = (T*)gx; o.gshift = (S*)gshift; o.ws = ws;
+    o.normalize = normalize_grad;
+    return run(c, o, stream);
 }
 
 // ---- training fusion (round 5): the shift applied to relu(bn2(z)) without the activation ever being stored
 // (fused_bn.bn_relu_shift2d; backbone.py:129-131 under models.py:71-79's 2-D variant).  RK_ERR_UNSUPPORTED (nothing launched) when
 // no fused kernel covers the configuration (quantize; column kernels switched off and a shape the streaming kernels do not take); the caller then normalises
 // with rk_bn_apply_affine_* and calls the plain entry points.
-// the column kernels' fused variants take what no streaming kernel does (fp32 planes the LDS-DMA kernels stream keep the
-// normalise pass + those kernels: they are the faster pair there)
-static bool col_bn_takes(const Dims2& d, int elem_size) {
-    if (!col2d::supported(0)) return false;
-    if (elem_size == 4) {
-        dma2d::FDims f;
-        if (dma2d::make_fdims(f, d, dma2d::kFramesF32, true) && bwd_ring_bytes(f.b, 1, 1) <= 64 * 1024) return false;
-    }
-    return true;
-}
 template <typename T>
-static int forward2_bn(const void* z, const float* ab, const float* shift, void* y, int N, int C, int H, int W, int sH, int sW,
-                       int pH, int pW, int quantize, rk_stream_t stream) {
+int forward2_bn(const void* z, const float* ab, const float* shift, void* y, int N, int C, int H, int W, int sH, int sW, int pH,
+                int pW, int quantize, rk_stream_t stream) {
     if (!z || !ab || !shift || !y) return RK_ERR_NULL_POINTER;
-    Dims2 d;
-    if (int rc = make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return rc;
-    if (quantize) return RK_ERR_UNSUPPORTED;
-    if (tile2d::launch_forward2_bn<T, float>((const T*)z, ab, shift, (T*)y, d, (hipStream_t)stream)) return launch_status();
-    if constexpr (sizeof(T) == 2) {                                  // raw 16-bit planes: 56 x 56, 112 x 112
-        if (raw16::launch_forward2_bn<T, float>((const T*)z, ab, shift, (T*)y, d, (hipStream_t)stream)) return launch_status();
-        if (stage2d::launch_forward2_bn<T, float>((const T*)z, ab, shift, (T*)y, d, (hipStream_t)stream)) return launch_status();   // 28 x 28
-    }
-    if (col_bn_takes(d, (int)sizeof(T))) {                           // the strided layers and the 7 x 7 planes
-        col2d::launch_forward_bn<T>((const T*)z, ab, shift, (T*)y, d, (hipStream_t)stream);
-        return launch_status();
-    }
-    return RK_ERR_UNSUPPORTED;
+    Call c{};
+    if (int rc = make_dims2(c.d, N, C, H, W, sH, sW, pH, pW)) return rc;
+    c.form = kForwardBn; c.elem = (int)sizeof(T); c.quantize = quantize;
+    c.align[kX] = al(z); c.align[kY] = al(y); c.align[kGx] = 16; c.align[kBn] = al(ab);
+    Ops<T, float> o{};
+    o.x = (const T*)z; o.shift = shift; o.y = (T*)y; o.ab = ab;
+    return run(c, o, stream);
 }
 template <typename T>
-static int backward2_bn(const void* gy, const void* z, const float* abmi, const float* shift, void* dz, float* gshift, float* k12,
-                        float* dgamma, float* dbeta, int N, int C, int H, int W, int sH, int sW, int pH, int pW,
-                        int normalize_grad, int quantize, void* ws, size_t ws_bytes, rk_stream_t stream) {
+int backward2_bn(const void* gy, const void* z, const float* abmi, const float* shift, void* dz, float* gshift, float* k12,
+                 float* dgamma, float* dbeta, int N, int C, int H, int W, int sH, int sW, int pH, int pW, int normalize_grad,
+                 int quantize, void* ws, size_t ws_bytes, rk_stream_t stream) {
     if (!gy || !z || !abmi || !shift || !dz || !gshift || !k12 || !dgamma || !dbeta) return RK_ERR_NULL_POINTER;
-    Dims2 d;
-    if (int rc = make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return rc;
+    Call c{};
+    if (int rc = make_dims2(c.d, N, C, H, W, sH, sW, pH, pW)) return rc;
     if (quantize) return RK_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < 2 * workspace2(d, 4)) return RK_ERR_WORKSPACE;
-    dma2d::BnFuse2 bn;
-    bn.abmi = reinterpret_cast<const float4*>(abmi);
-    bn.k12 = k12; bn.dgamma = dgamma; bn.dbeta = dbeta;
-    bn.inv_count = (float)(1.0 / ((double)N * H * W));
-    if (tile2d::launch_backward2_bn<T, float>((const T*)gy, (const T*)z, shift, (T*)dz, gshift, ws, normalize_grad, bn, d,
-                                              (hipStream_t)stream))
-        return launch_status();
-    if constexpr (sizeof(T) == 2) {
-        if (raw16::launch_backward2_bn<T, float>((const T*)gy, (const T*)z, shift, (T*)dz, gshift, ws, normalize_grad, bn, d,
-                                                 (hipStream_t)stream))
-            return launch_status();
-        if (stage2d::launch_backward2_bn<T, float>((const T*)gy, (const T*)z, shift, (T*)dz, gshift, ws, normalize_grad, bn, d,
-                                                   (hipStream_t)stream))
-            return launch_status();
-    }
-    if (col_bn_takes(d, (int)sizeof(T))) {
-        const int P = col2d::launch_backward_bn<T>((const T*)gy, (const T*)z, shift, (T*)dz, (float*)ws, bn.abmi, d,
-                                                   (hipStream_t)stream);
-        hipLaunchKernelGGL(col2d::k2d_finalize_bn, dim3(C), dim3(finalize_block(P)), 0, (hipStream_t)stream, (const float*)ws,
-                           gshift, k12, dgamma, dbeta, C, P, normalize_grad, bn.inv_count);
-        return launch_status();
-    }
-    return RK_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < 2 * workspace_bytes(c.d, shape_switches())) return RK_ERR_WORKSPACE;
+    c.form = kBackwardBn; c.elem = (int)sizeof(T); c.gshift = true;
+    c.align[kX] = al(z); c.align[kY] = al(gy); c.align[kGx] = al(dz); c.align[kBn] = al(abmi);
+    Ops<T, float> o{};
+    o.gy = (const T*)gy; o.x = (const T*)z; o.shift = shift; o.gx = (T*)dz; o.gshift = gshift; o.ws = ws;
+    o.normalize = normalize_grad;
+    o.bn.abmi = reinterpret_cast<const float4*>(abmi);
+    o.bn.k12 = k12; o.bn.dgamma = dgamma; o.bn.dbeta = dbeta;
+    o.bn.inv_count = (float)(1.0 / ((double)N * H * W));
+    return run(c, o, stream);
 }
 
 }  // namespace
@@ -229,7 +177,8 @@ extern "C" {
 size_t rk2d_backward_workspace_bytes(int N, int C, int H, int W, int sH, int sW, int pH, int pW, int elem_size) {
     Dims2 d;
     if (make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return 0;
-    return workspace2(d, elem_size == 8 ? 8 : 4);                  // partials are fp32 (fp64 for f64)
+    (void)elem_size;                                               // fp32 and fp64 partials share the 16-byte slot
+    return workspace_bytes(d, shape_switches());
 }
 
 #define RK_DEF_2D(SFX, TYPE, CTYPE)                                                                              \
@@ -269,26 +218,23 @@ RK_DEF_2D_MIXED(bf16, __hip_bfloat16)
 #undef RK_DEF_2D_MIXED
 
 // 1 when rk2d_forward_bn_* / rk2d_backward_bn_* have a fused kernel for this shape and storage size (4: fp32, 2: bf16), else 0:
-// lets a caller decide BEFORE it runs bn2's statistics (whose side effects -- running statistics -- must happen once)
+// lets a caller decide BEFORE it runs bn2's statistics (whose side effects -- running statistics -- must happen once).  The answer
+// is the planner's: both BN forms plan to RK_OK with every operand aligned.
 int rk2d_bn_fused_shape(int N, int C, int H, int W, int sH, int sW, int pH, int pW, int elem_size) {
-    Dims2 d;
-    if (make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return 0;
+    Call c{};
+    if (make_dims2(c.d, N, C, H, W, sH, sW, pH, pW)) return 0;
     if (elem_size != 4 && elem_size != 2) return 0;
-    if (col_bn_takes(d, elem_size)) return 1;                       // the column kernels take what the others below do not
-    if (elem_size == 4) { tile2d::TDims2 t; return tile2d::make_tdims<float, 14, 14>(t, d) ? 1 : 0; }
-    tile2d::TDims2 t;
-    if (tile2d::make_tdims<__hip_bfloat16, 14, 14>(t, d)) return 1;
-    dma2d::FDims f;
-    if (raw16::make_fdims8(f, d, raw16::kFramesRaw16) && bwd_ring_bytes(f.b, 1, 1) <= 64 * 1024 &&
-        raw16::make_fdims8(f, d, raw16::kFramesRaw16Fwd) && interp_ring_bytes(f.b, 2) <= 64 * 1024)
-        return 1;
-    if (dma2d::make_fdims(f, d, dma2d::kFrames16)) return 1;         // register-staged 16-bit planes: other W % 4 == 0 (28 x 28)
-    return 0;
+    c.elem = elem_size; c.gshift = true;
+    for (int& a : c.align) a = 16;
+    c.form = kForwardBn;
+    if (plan(c, shape_switches()).rc) return 0;
+    c.form = kBackwardBn;
+    return plan(c, shape_switches()).rc ? 0 : 1;
 }
 size_t rk2d_backward_bn_workspace_bytes(int N, int C, int H, int W, int sH, int sW, int pH, int pW) {
     Dims2 d;
     if (make_dims2(d, N, C, H, W, sH, sW, pH, pW)) return 0;
-    return 2 * workspace2(d, 4);                                   // four partials per (channel, group) instead of two
+    return 2 * workspace_bytes(d, shape_switches());               // four partials per (channel, group) instead of two
 }
 int rk2d_forward_bn_f32(const float* z, const float* ab, const float* shift, float* y, int N, int C, int H, int W, int sH,
                         int sW, int pH, int pW, int quantize, rk_stream_t stream) {
@@ -309,6 +255,31 @@ int rk2d_backward_bn_bf16_sf32(const void* gy, const void* z, const float* abmi,
                                int pW, int normalize_grad, int quantize, void* ws, size_t ws_bytes, rk_stream_t stream) {
     return backward2_bn<__hip_bfloat16>(gy, z, abmi, shift, dz, gshift, k12, dgamma, dbeta, N, C, H, W, sH, sW, pH, pW,
                                         normalize_grad, quantize, ws, ws_bytes, stream);
+}
+
+// Test hook: the planner with explicit switches and alignments (no device call).  form: 0 forward, 1 backward, 2 rk2d_forward_bn_*,
+// 3 rk2d_backward_bn_*; elem_size 4 / 8 / 2; aligned: two bits per operand (x / z, y or gy, gx / dz, the BN pack, from bit 0):
+// 2 = a multiple of 16 bytes, 1 = of 8, 0 = neither; shift_kernels: 0 auto, 1 column, 2 generic; cus: compute units.
+// out[0] = launches, out[1] = P, out[2] = k2d_finalize / k2d_finalize_bn follows as a launch of its own, then 11 ints per launch:
+// family (rk2d_plan.hpp), negate, bn, rounds, M, single, vec, quant, grid, block, dynamic LDS bytes.  Returns the call's status
+// as far as it does not depend on pointers.
+int rk_debug_2d_plan(int form, int elem_size, int N, int C, int H, int W, int sH, int sW, int pH, int pW, int quantize,
+                     int want_gshift, int aligned, int shift_kernels, int cus, int* out) {
+    Call c{};
+    if (int rc = make_dims2(c.d, N, C, H, W, sH, sW, pH, pW)) return rc;
+    c.form = (Form)form; c.elem = elem_size; c.quantize = quantize; c.gshift = want_gshift || form == kBackwardBn;
+    for (int i = 0; i < 4; ++i) c.align[i] = 8 * ((aligned >> (2 * i)) & 3);
+    const Plan pl = plan(c, Switches{(ShiftKernels)shift_kernels, cus});
+    if (!out) return pl.rc;
+    out[0] = pl.n; out[1] = pl.P; out[2] = pl.finalize;
+    for (int i = 0; i < 3; ++i) {
+        const Launch& l = pl.l[i];
+        const bool fin = l.family == kFinalize || l.family == kFinalizeBn;
+        const int v[11] = {l.family, l.c.negate, l.c.bn, l.c.rounds, l.c.M, l.c.single, l.c.vec, l.c.quant, (int)l.c.grid,
+                           i >= pl.n ? 0 : fin ? finalize_block(pl.P) : kBlock, (int)l.c.lds};
+        for (int k = 0; k < 11; ++k) out[3 + 11 * i + k] = v[k];
+    }
+    return pl.rc;
 }
 
 }  // extern "C"

@@ -462,10 +462,6 @@ __global__ __launch_bounds__(kBlock) void k2d_finalize_bn(const float* __restric
 }
 
 // ----------------------------------------------------------------------------------- host side
-inline bool supported(int quantize) {
-    return column_kernels_on() && !quantize;
-}
-
 // plane_elems: the plane the threads index (output plane for forward, input plane for backward)
 inline C2Dims make_c2dims(const Dims2& d, int plane_elems) {
     C2Dims cd;
@@ -488,68 +484,31 @@ inline unsigned grid_of(const C2Dims& cd) {
     return (unsigned)((groups + per_block - 1) / per_block);
 }
 
+// forward (ab: the bn2 variant's [2][C])
 template <typename T, typename S>
-inline void launch_forward(const T* x, const S* shift, T* y, const Dims2& d, hipStream_t stream) {
-    const C2Dims cd = make_c2dims(d, d.Ho * d.Wo);
-    const bool vec = cd.M == 4 && (d.Ho * d.Wo) % 4 == 0 && ((uintptr_t)y & 15) == 0;
-    if (cd.M == 1)
-        hipLaunchKernelGGL((k2d_forward_column<T, S, 1>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, x, shift, y, cd);
-    else if (vec)
-        hipLaunchKernelGGL((k2d_forward_column<T, S, 4, true>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, x, shift, y, cd);
-    else
-        hipLaunchKernelGGL((k2d_forward_column<T, S, 4>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, x, shift, y, cd);
+inline void launch_forward(const Cfg2& c, const C2Dims& cd, const T* x, const S* shift, T* y, const float* ab, hipStream_t stream) {
+    with_bn<kBnVariant<T, S>>(c, [&](auto BN) {
+        constexpr bool B = decltype(BN)::value;
+#define RK_C2_FWD(MM, VC) hipLaunchKernelGGL((k2d_forward_column<T, S, MM, VC, B>), dim3(c.grid), dim3(kBlock), 0, stream, x, shift, y, cd, ab)
+        if (c.M == 1) RK_C2_FWD(1, false);
+        else if (c.vec) RK_C2_FWD(4, true);
+        else RK_C2_FWD(4, false);
+#undef RK_C2_FWD
+    });
 }
-
-template <typename T>
-inline void launch_forward_bn(const T* z, const float* ab, const float* shift, T* y, const Dims2& d, hipStream_t stream) {
-    const C2Dims cd = make_c2dims(d, d.Ho * d.Wo);
-    const bool vec = cd.M == 4 && (d.Ho * d.Wo) % 4 == 0 && ((uintptr_t)y & 15) == 0;
-    if (cd.M == 1)
-        hipLaunchKernelGGL((k2d_forward_column<T, float, 1, false, true>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, z, shift,
-                           y, cd, ab);
-    else if (vec)
-        hipLaunchKernelGGL((k2d_forward_column<T, float, 4, true, true>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, z, shift,
-                           y, cd, ab);
-    else
-        hipLaunchKernelGGL((k2d_forward_column<T, float, 4, false, true>), dim3(grid_of(cd)), dim3(kBlock), 0, stream, z, shift,
-                           y, cd, ab);
-}
-
-inline int backward_partials(const Dims2& d) {
-    const C2Dims cd = make_c2dims(d, d.H * d.W);
-    return cd.ngroups * cd.nchunks;
-}
-
-// d(x) + d(shift) partials into ws[C][2][P]; returns P
+// d(x) + d(shift) partials (+ bn2's sums, abmi: the bn2 variant's pack) into ws[C][2 or 4][P]
 template <typename T, typename S>
-inline int launch_backward(const T* gy, const T* x, const S* shift, T* gx, typename Compute<T>::type* ws,
-                           const Dims2& d, hipStream_t stream) {
-    const C2Dims cd = make_c2dims(d, d.H * d.W);
-    const bool single = d.sH >= 2 && d.sW >= 2;
-    const bool vec = cd.M == 4 && (d.H * d.W) % 4 == 0 && (((uintptr_t)x | (uintptr_t)gx) & 15) == 0;
-#define RK_C2_BWD(MM, SG, VC) hipLaunchKernelGGL((k2d_backward_column<T, S, MM, SG, VC>), dim3(grid_of(cd)), dim3(kBlock), 0, \
-                                                 stream, gy, x, shift, gx, ws, cd)
-    if (cd.M == 1) { if (single) RK_C2_BWD(1, true, false); else RK_C2_BWD(1, false, false); }
-    else if (vec) { if (single) RK_C2_BWD(4, true, true); else RK_C2_BWD(4, false, true); }
-    else { if (single) RK_C2_BWD(4, true, false); else RK_C2_BWD(4, false, false); }
+inline void launch_backward(const Cfg2& c, const C2Dims& cd, const T* gy, const T* x, const S* shift, T* gx,
+                            typename Compute<T>::type* ws, const float4* abmi, hipStream_t stream) {
+    with_bn<kBnVariant<T, S>>(c, [&](auto BN) {
+        constexpr bool B = decltype(BN)::value;
+#define RK_C2_BWD(MM, SG, VC) hipLaunchKernelGGL((k2d_backward_column<T, S, MM, SG, VC, B>), dim3(c.grid), dim3(kBlock), 0, stream, gy, \
+                                                 x, shift, gx, ws, cd, abmi)
+        if (c.M == 1) { if (c.single) RK_C2_BWD(1, true, false); else RK_C2_BWD(1, false, false); }
+        else if (c.vec) { if (c.single) RK_C2_BWD(4, true, true); else RK_C2_BWD(4, false, true); }
+        else { if (c.single) RK_C2_BWD(4, true, false); else RK_C2_BWD(4, false, false); }
 #undef RK_C2_BWD
-    return cd.ngroups * cd.nchunks;
-}
-
-// the training fusion: d(bn2's output) + d(shift) + bn2's sums into ws[C][4][P]; returns P
-template <typename T>
-inline int launch_backward_bn(const T* gy, const T* z, const float* shift, T* dz, float* ws, const float4* abmi,
-                              const Dims2& d, hipStream_t stream) {
-    const C2Dims cd = make_c2dims(d, d.H * d.W);
-    const bool single = d.sH >= 2 && d.sW >= 2;
-    const bool vec = cd.M == 4 && (d.H * d.W) % 4 == 0 && (((uintptr_t)z | (uintptr_t)dz) & 15) == 0;
-#define RK_C2_BWD(MM, SG, VC) hipLaunchKernelGGL((k2d_backward_column<T, float, MM, SG, VC, true>), dim3(grid_of(cd)), \
-                                                 dim3(kBlock), 0, stream, gy, z, shift, dz, ws, cd, abmi)
-    if (cd.M == 1) { if (single) RK_C2_BWD(1, true, false); else RK_C2_BWD(1, false, false); }
-    else if (vec) { if (single) RK_C2_BWD(4, true, true); else RK_C2_BWD(4, false, true); }
-    else { if (single) RK_C2_BWD(4, true, false); else RK_C2_BWD(4, false, false); }
-#undef RK_C2_BWD
-    return cd.ngroups * cd.nchunks;
+    });
 }
 
 }  // namespace col2d

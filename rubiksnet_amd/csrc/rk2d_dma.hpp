@@ -391,11 +391,11 @@ __global__ __launch_bounds__(kBlock) void k2d_dma_backward(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side.
-// false = shape not handled here (stride / padding / W % 4 / RK_SHIFT_KERNELS)
+// Host side: the geometry (false = not a shape for these kernels: stride / padding / W % 4 / no banding) and launchers
+// that run a planned launch (rk2d_plan.hpp).
 inline bool make_fdims(FDims& f, const Dims2& d, int frames_per_group, bool backward = false) {
     const bool s1p0 = d.sH == 1 && d.sW == 1 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || d.W % 4 != 0 || d.W < 4 || !streaming_kernels_on()) return false;
+    if (!s1p0 || d.W % 4 != 0 || d.W < 4) return false;
     BDims& b = f.b;
     b.N = 1; b.T = d.N; b.C = d.C; b.H = d.H; b.W = d.W; b.W4 = d.W / 4;
     if (!choose_bands(b, backward)) return false;      // (backward: two-round bands, rk_dma.hpp)
@@ -408,52 +408,32 @@ inline bool make_fdims(FDims& f, const Dims2& d, int frames_per_group, bool back
 // 4: 73/111, 8: 76/114, 16: 73/115 -- many short-lived workgroups keep the read/write mix of the chip even;
 // the register-staged 16-bit kernels (deeper per-workgroup prologue) 2: 49/96, 4: 45/85, 8: 46/81, 16: 44/81.
 constexpr int kFramesF32 = 2, kFrames16 = 8;
+constexpr int kInterpDepth = 2;                        // prefetch depth D of k2d_dma_interp / k2d_raw16_interp
 
-template <bool NEGATE>
-inline bool launch_interp2(const float* src, const float* shift, float* dst, const Dims2& d, hipStream_t stream) {
-    constexpr int D = 2;
-    FDims f;
-    if (!make_fdims(f, d, kFramesF32) || !aligned16(src) || !aligned16(dst)) return false;
-    const size_t lds = interp_ring_bytes(f.b, D);
-    if (lds > 64 * 1024) return false;
-    const dim3 grid((unsigned)(f.ngroups * f.b.C * f.b.nbands)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_dma_interp<NEGATE, 1, D>), grid, block, lds, stream, src, shift, dst, f); break;
-        case 2: hipLaunchKernelGGL((k2d_dma_interp<NEGATE, 2, D>), grid, block, lds, stream, src, shift, dst, f); break;
-        case 3: hipLaunchKernelGGL((k2d_dma_interp<NEGATE, 3, D>), grid, block, lds, stream, src, shift, dst, f); break;
-        default: hipLaunchKernelGGL((k2d_dma_interp<NEGATE, 4, D>), grid, block, lds, stream, src, shift, dst, f); break;
-    }
-    return true;
-}
-
-// partials per channel the fused backward writes for this shape (0 = shape not handled here)
-inline int backward2_partials(const Dims2& d, int frames_per_group) {
-    FDims f;
-    return make_fdims(f, d, frames_per_group, true) ? f.ngroups * f.b.nbands : 0;
-}
-
-// d(x) + d(shift) (row-sum + K9 inside the launch: ws holds granules [C][2][P]); false = not handled here
-inline bool launch_backward2(const float* gy, const float* x, const float* shift, float* gx, float* gshift, void* ws,
-                             int normalize, const Dims2& d, hipStream_t stream) {
-    constexpr int DG = 1, DX = 1;
-    FDims f;
-    if (!make_fdims(f, d, kFramesF32, true) || !aligned16(gy) || !aligned16(x) || !aligned16(gx)) return false;
-    const size_t lds = bwd_ring_bytes(f.b, DG, DX);
-    if (lds > 64 * 1024) return false;
-    Fin2<float> fin;
+// the in-launch finalizers of a fused backward (row-sum + K9: ws holds granules [C][2 or 4][P]), armed for one launch
+template <typename S> inline Fin2<S> make_fin2(void* ws, int producers, S* gshift, int normalize) {
+    Fin2<S> fin;
     fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
     fin_arm(fin.f);
-    fin.f.producers = f.ngroups * f.b.C * f.b.nbands;
+    fin.f.producers = producers;
     fin.gshift = gshift;
     fin.normalize = normalize;
-    const dim3 grid((unsigned)(fin.f.producers + f.b.C)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_dma_backward<1, DG, DX>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-        case 2: hipLaunchKernelGGL((k2d_dma_backward<2, DG, DX>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-        case 3: hipLaunchKernelGGL((k2d_dma_backward<3, DG, DX>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-        default: hipLaunchKernelGGL((k2d_dma_backward<4, DG, DX>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-    }
-    return true;
+    return fin;
+}
+
+inline void launch_interp(const g2d::Cfg2& c, const FDims& f, const float* src, const float* shift, float* dst, hipStream_t stream) {
+    g2d::with_interp_variant<false>(c, [&](auto NEG, auto) { g2d::with_rounds(c.rounds, [&](auto R) {
+        hipLaunchKernelGGL((k2d_dma_interp<decltype(NEG)::value, decltype(R)::value, kInterpDepth>), dim3(c.grid), dim3(kBlock), c.lds,
+                           stream, src, shift, dst, f);
+    }); });
+}
+// d(x) + d(shift)
+inline void launch_backward(const g2d::Cfg2& c, const FDims& f, const Dims2& d, const float* gy, const float* x, const float* shift,
+                            float* gx, const Fin2<float>& fin, hipStream_t stream) {
+    g2d::with_rounds(c.rounds, [&](auto R) {
+        hipLaunchKernelGGL((k2d_dma_backward<decltype(R)::value, 1, 1>), dim3(c.grid), dim3(kBlock), c.lds, stream, gy, x, shift, gx, f,
+                           d, fin);
+    });
 }
 
 }  // namespace dma2d

@@ -5,6 +5,7 @@
 // in fp32 and rounded once on store; only the quantize position arithmetic is done in the storage type,
 // because it decides WHICH element is gathered (the reference instantiates the whole kernel at c10::Half).
 #pragma once
+#include <type_traits>
 #include "rk_common.hpp"
 
 namespace rk {
@@ -15,6 +16,44 @@ struct Dims2 {
     int sH, sW, pH, pW;
     int E, logE;
 };
+
+// What a planned launch (rk2d_plan.hpp) hands its family's launcher, which runs exactly that and decides nothing: the
+// template variant the launcher switches on, the grid and the dynamic LDS bytes.
+struct Cfg2 {
+    int negate;              // forward / d(x)-only kernels: src = gy, dst = gx, the negated shift
+    int bn;                  // the bn2 + ReLU variant (kBnVariant types only)
+    int rounds;              // band kernels: ROUNDS (1 .. 4)
+    int M, single, vec;      // column kernels: kM, SINGLE, VEC
+    int quant;               // generic kernels: QUANT
+    unsigned grid;
+    size_t lds;
+};
+// the storage types the bn2-fused entry points exist for (rk2d_*_bn_f32, rk2d_*_bn_bf16_sf32)
+template <typename T, typename S>
+constexpr bool kBnVariant = std::is_same<S, float>::value && (std::is_same<T, float>::value || std::is_same<T, __hip_bfloat16>::value);
+
+// f(std::integral_constant<int, ROUNDS>) for a planned ROUNDS; f(NEGATE, BN) for the planned forward / d(x)-only variant
+template <typename F> inline void with_rounds(int rounds, F&& f) {
+    switch (rounds) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+template <bool MAY_BN, typename F> inline void with_interp_variant(const Cfg2& c, F&& f) {
+    if constexpr (MAY_BN) {
+        if (c.bn) return f(std::false_type{}, std::true_type{});
+    }
+    if (c.negate) f(std::true_type{}, std::false_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+template <bool MAY_BN, typename F> inline void with_bn(const Cfg2& c, F&& f) {
+    if constexpr (MAY_BN) {
+        if (c.bn) return f(std::true_type{});
+    }
+    f(std::false_type{});
+}
 
 // rubiks2d_kernels.cu:69-73
 template <typename CT> __device__ __forceinline__ int floor_fast(CT v) {

@@ -404,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void k2d_raw16_backward(const T* __restrict
 #undef RK_OFF8_SWITCH
 
 // ---------------------------------------------------------------------------------------------
-// Host side.  false = shape not handled here (stride / padding / W % 8 / RK_SHIFT_KERNELS): rk2d_stage.hpp takes it.
+// Host side.  false = not a shape for these kernels (stride / padding / W % 8 / no banding): rk2d_stage.hpp takes it.
 // In BDims "W4" is cells per row = W / 8 here.
 // Frames per workgroup and band count do not matter here ([256,64,56,56] bf16, fwd / bwd us: 1 frame 37.6 / 57.3,
 // 2: 37.1 / 56.3, 4: 37.4 / 57.5, 8: 37.6 / 58.1, 16: 36.9 / 57.1; two 28-row bands: the same within 1 us).
@@ -414,7 +414,7 @@ constexpr int kFramesRaw16 = 4;                   // backward
 constexpr int kFramesRaw16Fwd = 2;                // forward / d(x) alone
 inline bool make_fdims8(FDims& f, const Dims2& d, int frames_per_group) {
     const bool s1p0 = d.sH == 1 && d.sW == 1 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || d.W % 8 != 0 || !streaming_kernels_on()) return false;
+    if (!s1p0 || d.W % 8 != 0) return false;
     BDims& b = f.b;
     b.N = 1; b.T = d.N; b.C = d.C; b.H = d.H; b.W = d.W; b.W4 = d.W / 8;
     if (!choose_bands(b)) return false;
@@ -423,90 +423,22 @@ inline bool make_fdims8(FDims& f, const Dims2& d, int frames_per_group) {
     f.ngroups = (d.N + f.FG - 1) / f.FG;
     return true;
 }
-inline int backward2_partials(const Dims2& d) {
-    FDims f;
-    return make_fdims8(f, d, kFramesRaw16) ? f.ngroups * f.b.nbands : 0;
-}
-
-template <typename T, bool NEGATE, typename S>
-inline bool launch_interp2(const T* src, const S* shift, T* dst, const Dims2& d, hipStream_t stream) {
-    constexpr int D = 2;
-    FDims f;
-    if (!make_fdims8(f, d, kFramesRaw16Fwd) || !aligned16(src) || !aligned16(dst)) return false;
-    const size_t lds = interp_ring_bytes(f.b, D);
-    if (lds > 64 * 1024) return false;
-    const dim3 grid((unsigned)(f.ngroups * f.b.C * f.b.nbands)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_raw16_interp<T, S, NEGATE, 1, D>), grid, block, lds, stream, src, shift, dst, f); break;
-        case 2: hipLaunchKernelGGL((k2d_raw16_interp<T, S, NEGATE, 2, D>), grid, block, lds, stream, src, shift, dst, f); break;
-        case 3: hipLaunchKernelGGL((k2d_raw16_interp<T, S, NEGATE, 3, D>), grid, block, lds, stream, src, shift, dst, f); break;
-        default: hipLaunchKernelGGL((k2d_raw16_interp<T, S, NEGATE, 4, D>), grid, block, lds, stream, src, shift, dst, f); break;
-    }
-    return true;
-}
-
-// d(x) + d(shift) (row-sum + K9 inside the launch: ws holds granules [C][2][P]); false = not handled here
+// forward (ab: the bn2 variant's [2][C]) or d(x) alone
 template <typename T, typename S>
-inline bool launch_backward2(const T* gy, const T* x, const S* shift, T* gx, S* gshift, void* ws, int normalize,
-                             const Dims2& d, hipStream_t stream) {
-    FDims f;
-    if (!make_fdims8(f, d, kFramesRaw16) || !aligned16(gy) || !aligned16(x) || !aligned16(gx)) return false;
-    const size_t lds = bwd_ring_bytes(f.b, 1, 1);
-    if (lds > 64 * 1024) return false;
-    Fin2<S> fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = f.ngroups * f.b.C * f.b.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    const dim3 grid((unsigned)(fin.f.producers + f.b.C)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 1>), grid, block, lds, stream, gy, x, shift, gx, f, fin); break;
-        case 2: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 2>), grid, block, lds, stream, gy, x, shift, gx, f, fin); break;
-        case 3: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 3>), grid, block, lds, stream, gy, x, shift, gx, f, fin); break;
-        default: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 4>), grid, block, lds, stream, gy, x, shift, gx, f, fin); break;
-    }
-    return true;
+inline void launch_interp(const g2d::Cfg2& c, const FDims& f, const T* src, const S* shift, T* dst, const float* ab, hipStream_t stream) {
+    g2d::with_interp_variant<g2d::kBnVariant<T, S>>(c, [&](auto NEG, auto BN) { g2d::with_rounds(c.rounds, [&](auto R) {
+        hipLaunchKernelGGL((k2d_raw16_interp<T, S, decltype(NEG)::value, decltype(R)::value, dma2d::kInterpDepth, decltype(BN)::value>),
+                           dim3(c.grid), dim3(kBlock), c.lds, stream, src, shift, dst, f, ab);
+    }); });
 }
-
-// training fusion: forward of relu(bn2(z)) (ab [2][C]) and its backward; false = not handled here
+// d(x) + d(shift) (+ bn2's sums)
 template <typename T, typename S>
-inline bool launch_forward2_bn(const T* z, const float* ab, const S* shift, T* y, const Dims2& d, hipStream_t stream) {
-    constexpr int D = 2;
-    FDims f;
-    if (!make_fdims8(f, d, kFramesRaw16Fwd) || !aligned16(z) || !aligned16(y)) return false;
-    const size_t lds = interp_ring_bytes(f.b, D);
-    if (lds > 64 * 1024) return false;
-    const dim3 grid((unsigned)(f.ngroups * f.b.C * f.b.nbands)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_raw16_interp<T, S, false, 1, D, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-        case 2: hipLaunchKernelGGL((k2d_raw16_interp<T, S, false, 2, D, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-        case 3: hipLaunchKernelGGL((k2d_raw16_interp<T, S, false, 3, D, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-        default: hipLaunchKernelGGL((k2d_raw16_interp<T, S, false, 4, D, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-    }
-    return true;
-}
-template <typename T, typename S>
-inline bool launch_backward2_bn(const T* gy, const T* z, const S* shift, T* dz, S* gshift, void* ws, int normalize,
-                                const dma2d::BnFuse2& bn, const Dims2& d, hipStream_t stream) {
-    FDims f;
-    if (!make_fdims8(f, d, kFramesRaw16) || !aligned16(gy) || !aligned16(z) || !aligned16(dz) || !aligned16(bn.abmi)) return false;
-    const size_t lds = bwd_ring_bytes(f.b, 1, 1);
-    if (lds > 64 * 1024) return false;
-    Fin2<S> fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = f.ngroups * f.b.C * f.b.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    const dim3 grid((unsigned)(fin.f.producers + f.b.C)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 1, true>), grid, block, lds, stream, gy, z, shift, dz, f, fin, bn); break;
-        case 2: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 2, true>), grid, block, lds, stream, gy, z, shift, dz, f, fin, bn); break;
-        case 3: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 3, true>), grid, block, lds, stream, gy, z, shift, dz, f, fin, bn); break;
-        default: hipLaunchKernelGGL((k2d_raw16_backward<T, S, 4, true>), grid, block, lds, stream, gy, z, shift, dz, f, fin, bn); break;
-    }
-    return true;
+inline void launch_backward(const g2d::Cfg2& c, const FDims& f, const T* gy, const T* x, const S* shift, T* gx, const Fin2<S>& fin,
+                            const dma2d::BnFuse2& bn, hipStream_t stream) {
+    g2d::with_bn<g2d::kBnVariant<T, S>>(c, [&](auto BN) { g2d::with_rounds(c.rounds, [&](auto R) {
+        hipLaunchKernelGGL((k2d_raw16_backward<T, S, decltype(R)::value, decltype(BN)::value>), dim3(c.grid), dim3(kBlock), c.lds, stream,
+                           gy, x, shift, gx, f, fin, bn);
+    }); });
 }
 
 }  // namespace raw16

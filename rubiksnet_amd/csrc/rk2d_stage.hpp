@@ -351,82 +351,25 @@ __global__ __launch_bounds__(kBlock) void k2d_stage_backward(const T* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// Host side: the geometry is dma2d::make_fdims at kFrames16 (8-byte cells: the operands need 8-byte alignment only).
 inline size_t ring_bytes(const BDims& b) { return (size_t)2 * ((b.BH + 1) * b.W4 + 1) * 16; }
 
-template <typename T, bool NEGATE, typename S>
-inline bool launch_interp2(const T* src, const S* shift, T* dst, const Dims2& d, hipStream_t stream) {
-    FDims f;
-    if (!dma2d::make_fdims(f, d, dma2d::kFrames16) || !aligned8(src) || !aligned8(dst)) return false;
-    const size_t lds = ring_bytes(f.b);
-    const dim3 grid((unsigned)(f.ngroups * f.b.C * f.b.nbands)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_stage_interp<T, S, NEGATE, 1>), grid, block, lds, stream, src, shift, dst, f); break;
-        case 2: hipLaunchKernelGGL((k2d_stage_interp<T, S, NEGATE, 2>), grid, block, lds, stream, src, shift, dst, f); break;
-        case 3: hipLaunchKernelGGL((k2d_stage_interp<T, S, NEGATE, 3>), grid, block, lds, stream, src, shift, dst, f); break;
-        default: hipLaunchKernelGGL((k2d_stage_interp<T, S, NEGATE, 4>), grid, block, lds, stream, src, shift, dst, f); break;
-    }
-    return true;
-}
-
-// d(x) + d(shift) (row-sum + K9 inside the launch: ws holds granules [C][2][P]); false = not handled here
+// forward (ab: the bn2 variant's [2][C]) or d(x) alone
 template <typename T, typename S>
-inline bool launch_backward2(const T* gy, const T* x, const S* shift, T* gx, S* gshift, void* ws, int normalize,
-                             const Dims2& d, hipStream_t stream) {
-    FDims f;
-    if (!dma2d::make_fdims(f, d, dma2d::kFrames16) || !aligned8(gy) || !aligned8(x) || !aligned8(gx)) return false;
-    const size_t lds = ring_bytes(f.b);
-    dma2d::Fin2<S> fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = f.ngroups * f.b.C * f.b.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    const dim3 grid((unsigned)(fin.f.producers + f.b.C)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_stage_backward<T, S, 1>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-        case 2: hipLaunchKernelGGL((k2d_stage_backward<T, S, 2>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-        case 3: hipLaunchKernelGGL((k2d_stage_backward<T, S, 3>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-        default: hipLaunchKernelGGL((k2d_stage_backward<T, S, 4>), grid, block, lds, stream, gy, x, shift, gx, f, d, fin); break;
-    }
-    return true;
+inline void launch_interp(const g2d::Cfg2& c, const FDims& f, const T* src, const S* shift, T* dst, const float* ab, hipStream_t stream) {
+    g2d::with_interp_variant<g2d::kBnVariant<T, S>>(c, [&](auto NEG, auto BN) { g2d::with_rounds(c.rounds, [&](auto R) {
+        hipLaunchKernelGGL((k2d_stage_interp<T, S, decltype(NEG)::value, decltype(R)::value, decltype(BN)::value>), dim3(c.grid),
+                           dim3(kBlock), c.lds, stream, src, shift, dst, f, ab);
+    }); });
 }
-
-// training fusion: forward of relu(bn2(z)) (ab [2][C]) and its backward; false = not handled here
+// d(x) + d(shift) (+ bn2's sums)
 template <typename T, typename S>
-inline bool launch_forward2_bn(const T* z, const float* ab, const S* shift, T* y, const Dims2& d, hipStream_t stream) {
-    FDims f;
-    if (!dma2d::make_fdims(f, d, dma2d::kFrames16) || !aligned8(z) || !aligned8(y)) return false;
-    const size_t lds = ring_bytes(f.b);
-    const dim3 grid((unsigned)(f.ngroups * f.b.C * f.b.nbands)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_stage_interp<T, S, false, 1, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-        case 2: hipLaunchKernelGGL((k2d_stage_interp<T, S, false, 2, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-        case 3: hipLaunchKernelGGL((k2d_stage_interp<T, S, false, 3, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-        default: hipLaunchKernelGGL((k2d_stage_interp<T, S, false, 4, true>), grid, block, lds, stream, z, shift, y, f, ab); break;
-    }
-    return true;
-}
-template <typename T, typename S>
-inline bool launch_backward2_bn(const T* gy, const T* z, const S* shift, T* dz, S* gshift, void* ws, int normalize,
-                                const dma2d::BnFuse2& bn, const Dims2& d, hipStream_t stream) {
-    FDims f;
-    if (!dma2d::make_fdims(f, d, dma2d::kFrames16) || !aligned8(gy) || !aligned8(z) || !aligned8(dz) || !aligned16(bn.abmi)) return false;
-    const size_t lds = ring_bytes(f.b);
-    dma2d::Fin2<S> fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = f.ngroups * f.b.C * f.b.nbands;
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    const dim3 grid((unsigned)(fin.f.producers + f.b.C)), block(kBlock);
-    switch (rounds_of(f.b)) {
-        case 1: hipLaunchKernelGGL((k2d_stage_backward<T, S, 1, true>), grid, block, lds, stream, gy, z, shift, dz, f, d, fin, bn); break;
-        case 2: hipLaunchKernelGGL((k2d_stage_backward<T, S, 2, true>), grid, block, lds, stream, gy, z, shift, dz, f, d, fin, bn); break;
-        case 3: hipLaunchKernelGGL((k2d_stage_backward<T, S, 3, true>), grid, block, lds, stream, gy, z, shift, dz, f, d, fin, bn); break;
-        default: hipLaunchKernelGGL((k2d_stage_backward<T, S, 4, true>), grid, block, lds, stream, gy, z, shift, dz, f, d, fin, bn); break;
-    }
-    return true;
+inline void launch_backward(const g2d::Cfg2& c, const FDims& f, const Dims2& d, const T* gy, const T* x, const S* shift, T* gx,
+                            const dma2d::Fin2<S>& fin, const dma2d::BnFuse2& bn, hipStream_t stream) {
+    g2d::with_bn<g2d::kBnVariant<T, S>>(c, [&](auto BN) { g2d::with_rounds(c.rounds, [&](auto R) {
+        hipLaunchKernelGGL((k2d_stage_backward<T, S, decltype(R)::value, decltype(BN)::value>), dim3(c.grid), dim3(kBlock), c.lds, stream,
+                           gy, x, shift, gx, f, d, fin, bn);
+    }); });
 }
 
 }  // namespace stage2d

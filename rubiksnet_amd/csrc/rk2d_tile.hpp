@@ -457,7 +457,7 @@ void k2d_tile_backward(const T* __restrict__ gy, const T* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side.  false / 0 = shape not handled here.
+// Host side.  false = not a shape for these kernels.
 // frames per wave, [256,288,14,14] fwd / bwd us (steady state): bf16 1: 22 / 44, 2: 19 / 31, 4: 17 / 26, 8: 17 / 26,
 // 16: 19 / 28, 32: 26 / 40, 64: 45 / 62; fp32 1: 22 / 50, 2: 21 / 40, 4: 22.5 / 35, 8: 24 / 36, 16: 27 / 42, 32: 30 / 46
 // The backward of the 16-bit types (3 waves per SIMD) in ONE round of resident waves: with 4 frames per wave [256,288,14,14] is
@@ -466,14 +466,15 @@ void k2d_tile_backward(const T* __restrict__ gy, const T* __restrict__ x,
 // us plain / fused: 4: 25.8 / 34.4, 6: 25.1 / 33.7, 8: 26.2 / 34.0, 10: 25.0 / 35.1, 12: 24.3 / 30.5, 13: 24.9 / 31.8, 14: 26.0 /
 // 33.6, 16: 28.2 / 36.9 -- the optimum is the round boundary; the forward is best at 4: 14.4 / 15.7 us against 15.5 / 17.6 at 12).
 constexpr int kTileFrames = 4;
-template <typename T, int H, int W> inline bool make_tdims(TDims2& t, const Dims2& d, bool backward = false) {
+// cus: the device's compute units (the frames per wave of the 16-bit backward)
+template <typename T, int H, int W> inline bool make_tdims(TDims2& t, const Dims2& d, bool backward, int cus) {
     using G = Geo<T, H, W>;
     const bool s1p0 = d.sH == 1 && d.sW == 1 && d.pH == 0 && d.pW == 0;
-    if (!s1p0 || d.H != H || d.W != W || d.C % G::GC != 0 || !streaming_kernels_on()) return false;
+    if (!s1p0 || d.H != H || d.W != W || d.C % G::GC != 0) return false;
     t.F = d.N; t.C = d.C; t.NG = d.C / G::GC;
     int fg = kTileFrames;
     if (backward && sizeof(T) == 2) {
-        const long long slots = (long long)device_cus() * 12;       // 3 waves per SIMD
+        const long long slots = (long long)cus * 12;                // 3 waves per SIMD
         const long long want = ((long long)d.N * t.NG + slots - 1) / slots;
         fg = (int)(want < kTileFrames ? kTileFrames : (want > 16 ? 16 : want));
     }
@@ -481,75 +482,30 @@ template <typename T, int H, int W> inline bool make_tdims(TDims2& t, const Dims
     t.ngroups = (d.N + t.FG - 1) / t.FG;
     return true;
 }
-template <typename T> inline int backward2_partials(const Dims2& d) {
-    TDims2 t;
-    return make_tdims<T, 14, 14>(t, d, true) ? t.ngroups : 0;
-}
+constexpr int kInterpSlots = 4, kBackwardSlots = 3;   // ring slots R (the forward's static full-group schedule was tried in the
+                                                      // backward too: 245 VGPRs, 26 -> 31 us)
+// dynamic LDS of a 4-wave workgroup (the slot stride is the same for every storage type: 784 + 16 bytes)
+inline size_t interp_lds() { return (size_t)4 * kInterpSlots * Geo<float, 14, 14>::STRIDE; }
+inline size_t backward_lds() { return (size_t)4 * 2 * kBackwardSlots * Geo<float, 14, 14>::STRIDE; }
+static_assert(Geo<float, 14, 14>::STRIDE == Geo<__half, 14, 14>::STRIDE && Geo<float, 14, 14>::STRIDE == Geo<__hip_bfloat16, 14, 14>::STRIDE,
+              "one slot stride");
 
-template <typename T, bool NEGATE, typename S>
-inline bool launch_interp2(const T* src, const S* shift, T* dst, const Dims2& d, hipStream_t stream) {
-    constexpr int R = 4;
-    using G = Geo<T, 14, 14>;
-    TDims2 t;
-    if (!make_tdims<T, 14, 14>(t, d) || !aligned16(src) || !aligned16(dst)) return false;
-    const long long waves = (long long)t.NG * t.ngroups;
-    const size_t lds = (size_t)4 * R * G::STRIDE;
-    hipLaunchKernelGGL((k2d_tile_interp<T, S, 14, 14, R, NEGATE>), dim3((unsigned)((waves + 3) / 4)), dim3(kBlock), lds, stream,
-                       src, shift, dst, t);
-    return true;
-}
-
+// forward (ab: the bn2 variant's [2][C]) or d(x) alone
 template <typename T, typename S>
-inline bool launch_backward2(const T* gy, const T* x, const S* shift, T* gx, S* gshift, void* ws, int normalize,
-                             const Dims2& d, hipStream_t stream) {
-    constexpr int R = 3;       // (the forward's static full-group schedule was tried here too: 245 VGPRs, 26 -> 31 us)
-    using G = Geo<T, 14, 14>;
-    TDims2 t;
-    if (!make_tdims<T, 14, 14>(t, d, true) || !aligned16(gy) || !aligned16(x) || !aligned16(gx)) return false;
-    const long long waves = (long long)t.NG * t.ngroups;
-    const size_t lds = (size_t)4 * 2 * R * G::STRIDE;
-    Fin2<S> fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = (int)((waves + 3) / 4);
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    hipLaunchKernelGGL((k2d_tile_backward<T, S, 14, 14, R>), dim3((unsigned)(fin.f.producers + t.C)), dim3(kBlock), lds, stream, gy,
-                       x, shift, gx, t, fin);
-    return true;
+inline void launch_interp(const g2d::Cfg2& c, const TDims2& t, const T* src, const S* shift, T* dst, const float* ab, hipStream_t stream) {
+    g2d::with_interp_variant<g2d::kBnVariant<T, S>>(c, [&](auto NEG, auto BN) {
+        hipLaunchKernelGGL((k2d_tile_interp<T, S, 14, 14, kInterpSlots, decltype(NEG)::value, decltype(BN)::value>), dim3(c.grid),
+                           dim3(kBlock), c.lds, stream, src, shift, dst, t, ab);
+    });
 }
-
-// training fusion: forward of relu(bn2(z)) (ab [2][C]) and its backward; false = shape not handled here
+// d(x) + d(shift) (+ bn2's sums)
 template <typename T, typename S>
-inline bool launch_forward2_bn(const T* z, const float* ab, const S* shift, T* y, const Dims2& d, hipStream_t stream) {
-    constexpr int R = 4;
-    using G = Geo<T, 14, 14>;
-    TDims2 t;
-    if (!make_tdims<T, 14, 14>(t, d) || !aligned16(z) || !aligned16(y)) return false;
-    const long long waves = (long long)t.NG * t.ngroups;
-    const size_t lds = (size_t)4 * R * G::STRIDE;
-    hipLaunchKernelGGL((k2d_tile_interp<T, S, 14, 14, R, false, true>), dim3((unsigned)((waves + 3) / 4)), dim3(kBlock), lds, stream,
-                       z, shift, y, t, ab);
-    return true;
-}
-template <typename T, typename S>
-inline bool launch_backward2_bn(const T* gy, const T* z, const S* shift, T* dz, S* gshift, void* ws, int normalize,
-                                const BnFuse2& bn, const Dims2& d, hipStream_t stream) {
-    constexpr int R = 3;
-    using G = Geo<T, 14, 14>;
-    TDims2 t;
-    if (!make_tdims<T, 14, 14>(t, d, true) || !aligned16(gy) || !aligned16(z) || !aligned16(dz) || !aligned16(bn.abmi)) return false;
-    const long long waves = (long long)t.NG * t.ngroups;
-    const size_t lds = (size_t)4 * 2 * R * G::STRIDE;
-    Fin2<S> fin;
-    fin.f.gran = reinterpret_cast<unsigned long long*>(ws);
-    fin_arm(fin.f);
-    fin.f.producers = (int)((waves + 3) / 4);
-    fin.gshift = gshift;
-    fin.normalize = normalize;
-    hipLaunchKernelGGL((k2d_tile_backward<T, S, 14, 14, R, true>), dim3((unsigned)(fin.f.producers + t.C)), dim3(kBlock), lds, stream,
-                       gy, z, shift, dz, t, fin, bn);
-    return true;
+inline void launch_backward(const g2d::Cfg2& c, const TDims2& t, const T* gy, const T* x, const S* shift, T* gx, const Fin2<S>& fin,
+                            const BnFuse2& bn, hipStream_t stream) {
+    g2d::with_bn<g2d::kBnVariant<T, S>>(c, [&](auto BN) {
+        hipLaunchKernelGGL((k2d_tile_backward<T, S, 14, 14, kBackwardSlots, decltype(BN)::value>), dim3(c.grid), dim3(kBlock), c.lds,
+                           stream, gy, x, shift, gx, t, fin, bn);
+    });
 }
 
 }  // namespace tile2d
