@@ -690,6 +690,27 @@ int rk_clip_resample_u8_f32(const unsigned char* frames, const int* boxes, const
                             float* out, int B, int T, int Hs, int Ws, int V, int Sh, int Sw, rk_stream_t stream);
 int rk_clip_resample_u8_bf16(const unsigned char* frames, const int* boxes, const float* mean3, const float* std3,
                              void* out, int B, int T, int Hs, int Ws, int V, int Sh, int Sw, rk_stream_t stream);
+/* The same pass from a packed arena of B videos of different sizes (rubiksnet/dataset/core.py decodes a list of PIL
+ * images per sample; real sets are ragged: one height and many widths, or both).  arena: uint8, arena_bytes long, any
+ * alignment.  clips: device int64 [B, 4], one record per video: (byte offset of its first frame in the arena, Hs, Ws, F);
+ * its F frames [Hs, Ws, 3] lie back to back from that offset, rows Ws * 3 bytes apart, no padding, and the offset may be
+ * any byte.  frame_idx: device int32 [B * V, T]: output frame t of output clip oc shows stored frame
+ * clamp(frame_idx[oc, t], 0, F - 1) of video oc / V, so one video can give several temporal clips (the two-clip
+ * protocol) and frames may repeat.  boxes [B * V, 9], mean3, std3, out [B * V, T, 3, Sh, Sw] and the arithmetic are those
+ * of rk_clip_resample_u8_*: a batch whose videos happen to share one size, with frame_idx[oc, t] = t, gives the same bits.
+ * The tables are device data the launcher cannot check; the kernel never reads outside [arena, arena + arena_bytes),
+ * whatever they hold.  A record is INVALID when Hs or Ws is outside [1, 16384], F < 1, the offset is negative, or
+ * offset + F * Hs * Ws * 3 > arena_bytes: every workgroup of such a video's output clips decides that from the record
+ * alone, before its first read of the arena, and writes zeros.  Boxes are clamped as above, into the record's own frame.
+ * (rubiksnet_amd.augment.ragged_u8_to_clips checks host tables before they travel.)  B * V and T at most 65535;
+ * RK_ERR_UNSUPPORTED when Sw needs more LDS than a workgroup has (the source sizes do not enter); no workspace, no
+ * allocation, no host synchronisation.                                                                             */
+int rk_clip_resample_ragged_u8_f32(const unsigned char* arena, long long arena_bytes, const long long* clips,
+                                   const int* frame_idx, const int* boxes, const float* mean3, const float* std3,
+                                   float* out, int B, int V, int T, int Sh, int Sw, rk_stream_t stream);
+int rk_clip_resample_ragged_u8_bf16(const unsigned char* arena, long long arena_bytes, const long long* clips,
+                                    const int* frame_idx, const int* boxes, const float* mean3, const float* std3,
+                                    void* out, int B, int V, int T, int Sh, int Sw, rk_stream_t stream);
 
 /* ---- squeeze-and-excitation gate of RubiksNet-Small -- widening row f3 of SURVEY 8(f) --------------
  * SELayer (rubiksnet/backbone.py:56-71): y = x * sigmoid(W2 relu(W1 mean_hw(x))).  x, y, dy, dx [F, C, P];

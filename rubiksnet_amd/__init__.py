@@ -5,10 +5,12 @@ RubiksShift3D, RubiksShiftBase + functionals), `AttentionShift`, `RubiksNetBackb
 `RubiksNet`.  All device work goes through librubiks_hip.so (include/rubiks_hip.h);
 importing the package does not load it, calling an operator does.  `fin_status` reports an in-launch
 reduction that gave up (its outputs are NaN) as a RubiksHipError; `metrics.StreamMeter` accumulates loss, top-k and per-class
-accuracy on the device.
+accuracy on the device; `dataset` reads real video sets (list files, the reference's frame sampling) and feeds them through
+the device crop / resize / flip.
 """
 from . import shiftlib  # noqa: F401
 from . import augment  # noqa: F401
+from . import dataset  # noqa: F401
 from . import fin_status  # noqa: F401
 from . import optim  # noqa: F401
 from . import metrics  # noqa: F401
@@ -19,5 +21,5 @@ from .models import RubiksNet
 from .shiftlib import RubiksShift2D, RubiksShift3D, RubiksShiftBase
 
 __all__ = ["RubiksNet", "RubiksNetBackbone", "AttentionShift", "RubiksShift2D", "RubiksShift3D",
-           "RubiksShiftBase", "shiftlib", "augment", "fin_status", "optim", "metrics", "StreamMeter"]
+           "RubiksShiftBase", "shiftlib", "augment", "dataset", "fin_status", "optim", "metrics", "StreamMeter"]
 __version__ = "0.1.0"

@@ -162,6 +162,8 @@ for _sfx in ("f32", "bf16", "f16"):
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw
+    # arena, arena_bytes, clips, frame_idx, boxes, mean3, std3, out, B, V, T, Sh, Sw, stream
+    SIGNATURES["rk_clip_resample_ragged_u8_" + _sfx] = (_i, [_p, ctypes.c_longlong] + [_p] * 6 + [_i] * 5 + [_p])
     SIGNATURES["rk_se_squeeze_" + _sfx] = (_i, [_p, _p, _i, _i, _i, _p])
     SIGNATURES["rk_se_scale_" + _sfx] = (_i, [_p, _p, _p, _i, _i, _i, _p])
     SIGNATURES["rk_se_scale_backward_" + _sfx] = (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p])

@@ -9,6 +9,10 @@ the host only draws BOXES -- nine int32 per output clip, `(x0, y0, cw, ch, rw, r
 [oy : oy + Sh, ox : ox + Sw] -> mirror if flip -> ((v / 255) - mean) / std.  The fp32 result is bit-identical to the
 reference's chain; all T frames of a clip share one box, as in the reference.
 
+Real sets are ragged (one height and many widths, or both) and a clip is a choice of frames of a longer video:
+`ragged_u8_to_clips` (rk_clip_resample_ragged_u8_*) is the same pass from a packed byte arena with one record per video
+and a per-frame index table; `per_clip_boxes` draws each clip's boxes for its own frame size (dataset.py feeds it).
+
 Sizes follow the project's (height, width) order: `frame_hw`, `out_hw`; an int means a square.  The random draws come
 from a `torch.Generator` (the set of choices is the reference's, the stream is not Python's `random`).
 """
@@ -19,10 +23,11 @@ from .input_pipeline import IMAGENET_MEAN, IMAGENET_STD, _SFX, _mean_std_on, _ne
 
 __all__ = ["multiscale_crop_boxes", "center_crop_boxes", "full_res_boxes", "oversample_boxes", "check_boxes",
            "crop_candidates", "fix_offsets", "short_edge_size", "frames_u8_to_clips", "SyntheticFrameLoader",
-           "MAX_RATIO", "BOX_FIELDS"]
+           "MAX_RATIO", "BOX_FIELDS", "per_clip_boxes", "check_ragged", "ragged_u8_to_clips", "MAX_SIDE"]
 
 BOX_FIELDS = ("x0", "y0", "cw", "ch", "rw", "rh", "ox", "oy", "flip")
 MAX_RATIO = 8          # cw / rw and ch / rh: 17 filter taps (csrc/rk_resample.hip kTaps)
+MAX_SIDE = 16384       # the largest Hs or Ws a record of the ragged entry may claim (csrc/rk_resample.hip kMaxSide)
 
 
 def _hw(size):
@@ -191,6 +196,115 @@ def frames_u8_to_clips(frames, boxes, out_hw, views=1, mean=IMAGENET_MEAN, std=I
                 frames.data_ptr(), boxes.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr(), out.data_ptr(), B, T, Hs, Ws,
                 views, sh, sw, torch.cuda.current_stream(dev).cuda_stream)
         _native.check(rc, "rk_clip_resample_u8")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------- videos of different sizes
+def per_clip_boxes(sizes, fn):
+    """Boxes for clips whose frames differ in size: `fn((H, W))` -> int32 [views, 9] is called once per entry of `sizes`
+    (an iterable of (H, W)), e.g. `lambda hw: full_res_boxes(1, hw, 224, flip=False)`, and must return the same number of
+    views every time.  Returns int32 [len(sizes) * views, 9], clip-major: what ragged_u8_to_clips takes."""
+    rows, views = [], None
+    for i, hw in enumerate(sizes):
+        b = torch.as_tensor(fn(_hw(hw)))
+        if b.dim() != 2 or b.shape[1] != 9 or b.dtype != torch.int32 or b.shape[0] < 1:
+            raise ValueError("fn must return int32 [views, 9], got %s %s for clip %d" % (b.dtype, tuple(b.shape), i))
+        if views is None:
+            views = b.shape[0]
+        elif b.shape[0] != views:
+            raise ValueError("fn returned %d views for clip %d and %d for the clips before it" % (b.shape[0], i, views))
+        rows.append(b)
+    return torch.cat(rows) if rows else torch.zeros(0, 9, dtype=torch.int32)
+
+
+def check_ragged(arena_bytes, clips, frame_idx, boxes, out_hw, views=1):
+    """Raise ValueError unless the host tables describe a launch rk_clip_resample_ragged_u8_* defines a picture for:
+    clips int64 [B, 4] of (byte offset, Hs, Ws, F) with every record inside `arena_bytes`, frame_idx int32 [B * views, T]
+    with every index a stored frame of its own video, boxes int32 [B * views, 9] each valid for its own video's frame size
+    (check_boxes).  Pure CPU; returns (B, T)."""
+    views = int(views)
+    if views < 1:
+        raise ValueError("views must be >= 1")
+    clips, frame_idx, boxes = torch.as_tensor(clips), torch.as_tensor(frame_idx), torch.as_tensor(boxes)
+    if clips.is_cuda or frame_idx.is_cuda or boxes.is_cuda:
+        raise ValueError("check_ragged checks host tables (device tables are trusted)")
+    if clips.dim() != 2 or clips.shape[1] != 4 or clips.dtype != torch.int64:
+        raise ValueError("clips must be int64 [B, 4] (byte offset, Hs, Ws, F), got %s %s" % (clips.dtype, tuple(clips.shape)))
+    B = clips.shape[0]
+    if frame_idx.dim() != 2 or frame_idx.shape[0] != B * views or frame_idx.dtype != torch.int32:
+        raise ValueError("frame_idx must be int32 [B * views, T] = [%d, T], got %s %s" % (B * views, frame_idx.dtype,
+                                                                                        tuple(frame_idx.shape)))
+    if tuple(boxes.shape) != (B * views, 9) or boxes.dtype != torch.int32:
+        raise ValueError("boxes must be int32 [B * views, 9] = [%d, 9], got %s %s" % (B * views, boxes.dtype, tuple(boxes.shape)))
+    for b, (off, hs, ws, nf) in enumerate(clips.tolist()):
+        if not (1 <= hs <= MAX_SIDE and 1 <= ws <= MAX_SIDE):
+            raise ValueError("clip %d: frame size %dx%d outside [1, %d]" % (b, hs, ws, MAX_SIDE))
+        if nf < 1:
+            raise ValueError("clip %d: %d frames" % (b, nf))
+        if off < 0 or off + nf * hs * ws * 3 > arena_bytes:
+            raise ValueError("clip %d: bytes [%d, %d) lie outside the arena of %d bytes" % (b, off, off + nf * hs * ws * 3,
+                                                                                         arena_bytes))
+        idx = frame_idx[b * views:(b + 1) * views]
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= nf):
+            raise ValueError("clip %d: frame index outside [0, %d)" % (b, nf))
+        try:
+            check_boxes(boxes[b * views:(b + 1) * views], (hs, ws), out_hw)
+        except ValueError as e:
+            raise ValueError("clip %d: %s" % (b, e)) from None
+    return B, frame_idx.shape[1]
+
+
+def ragged_u8_to_clips(arena, clips, frame_idx, boxes, out_hw, views=1, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                       dtype=torch.float32, out=None):
+    """frames_u8_to_clips for videos of different sizes and chosen frames (rk_clip_resample_ragged_u8_*).  arena: uint8
+    [bytes] on the GPU, contiguous: the videos back to back (dataset.pack_clips).  clips: int64 [B, 4], per video (byte
+    offset of its first frame, Hs, Ws, F).  frame_idx: int32 [B * views, T], the stored frame (0-based) each output frame
+    shows.  boxes: int32 [B * views, 9], each for its own video's frame size.  Tables on the CPU are checked (check_ragged)
+    and copied through pinned memory without blocking; tables on the device are trusted (the kernel clamps indices and
+    boxes, and writes zeros for a record that does not fit the arena).  Returns [B * views, T, 3, Sh, Sw] in `dtype`."""
+    if dtype not in _SFX:
+        raise ValueError("dtype must be float32 or bfloat16, got %s" % dtype)
+    views = int(views)
+    if views < 1:
+        raise ValueError("views must be >= 1")
+    if not (torch.is_tensor(arena) and arena.dtype == torch.uint8 and arena.dim() == 1):
+        raise ValueError("arena must be a uint8 tensor [bytes]")
+    sh, sw = _hw(out_hw)
+    tables = (clips, frame_idx, boxes)
+    if all(not t.is_cuda for t in tables):
+        B, T = check_ragged(arena.numel(), clips, frame_idx, boxes, (sh, sw), views)
+    elif all(t.is_cuda for t in tables):
+        if clips.dim() != 2 or clips.shape[1] != 4 or clips.dtype != torch.int64:
+            raise ValueError("clips must be int64 [B, 4], got %s %s" % (clips.dtype, tuple(clips.shape)))
+        B = clips.shape[0]
+        if frame_idx.dim() != 2 or frame_idx.shape[0] != B * views or frame_idx.dtype != torch.int32:
+            raise ValueError("frame_idx must be int32 [B * views, T] = [%d, T], got %s %s" % (B * views, frame_idx.dtype,
+                                                                                            tuple(frame_idx.shape)))
+        if tuple(boxes.shape) != (B * views, 9) or boxes.dtype != torch.int32:
+            raise ValueError("boxes must be int32 [B * views, 9] = [%d, 9], got %s %s" % (B * views, boxes.dtype,
+                                                                                         tuple(boxes.shape)))
+        T = frame_idx.shape[1]
+    else:
+        raise ValueError("clips, frame_idx and boxes must be all on the CPU (checked) or all on the device (trusted)")
+    if not (arena.is_cuda and arena.is_contiguous()):
+        raise RuntimeError("arena must be a contiguous CUDA (HIP) uint8 tensor (no CPU fallback)")
+    dev = arena.device
+    if clips.is_cuda:
+        if any(t.device != dev or not t.is_contiguous() for t in tables):
+            raise RuntimeError("device tables must be contiguous and on the arena's device")
+    else:
+        clips, frame_idx, boxes = (t.contiguous().pin_memory().to(dev, non_blocking=True) for t in tables)
+    if out is None:
+        out = torch.empty(B * views, T, 3, sh, sw, dtype=dtype, device=dev)
+    elif tuple(out.shape) != (B * views, T, 3, sh, sw) or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError("out must be a contiguous %s tensor [B * views, T, 3, Sh, Sw] on the arena's device" % dtype)
+    ms = _mean_std_on(dev, mean, std)
+    if B and T:
+        with torch.cuda.device(dev):
+            rc = getattr(_native.lib(), "rk_clip_resample_ragged_u8_" + _SFX[dtype])(
+                arena.data_ptr(), arena.numel(), clips.data_ptr(), frame_idx.data_ptr(), boxes.data_ptr(), ms[0].data_ptr(),
+                ms[1].data_ptr(), out.data_ptr(), B, views, T, sh, sw, torch.cuda.current_stream(dev).cuda_stream)
+        _native.check(rc, "rk_clip_resample_ragged_u8")
     return out
 
 

@@ -27,6 +27,10 @@
 // clamped into the frame where it is formed; the rows of a vertical pass are chosen so that their taps lie inside the
 // LDS row buffer.  None of this changes a valid box's result, and a meaningless box gives a meaningless picture and
 // nothing else.
+//
+// rk_clip_resample_ragged_u8_* is the same pass for real datasets, whose videos differ in size and whose clips are
+// chosen frames of longer videos: the source is a packed arena, a record per video says where its frames lie and how
+// large they are, and a per-frame index table says which stored frame each output frame shows (k_clip_resample_ragged).
 #include "rk_common.hpp"
 
 using namespace rk;
@@ -38,6 +42,7 @@ constexpr int kBandRows = 16;      // output rows per workgroup
 constexpr int kHRows = 32;         // horizontally resampled source rows held in LDS (>= kTaps: one output row always fits)
 constexpr int kRowsPerIter = 4;    // source rows a lane resamples together in the horizontal pass
 constexpr int kPrec = 22;          // Pillow's PRECISION_BITS for 8-bit data (32 - 8 - 2)
+constexpr int kMaxSide = 16384;    // the largest Hs or Ws a record of the ragged entry may claim
 
 __device__ __forceinline__ double tri(double a) {
     if (a < 0.0) a = -a;
@@ -78,11 +83,12 @@ __host__ __device__ inline size_t resample_lds_bytes(int Sw) {
            (size_t)kHRows * Sw * 3;
 }
 
+// One workgroup's share of the work: band blockIdx.x of output frame t of output clip oc, from the source frame at fbase
+// (Hs x Ws x 3, rows Ws * 3 bytes apart).  Both kernels below are this body behind a different way of finding fbase.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_clip_resample(const unsigned char* __restrict__ frames,
-                                                          const int* __restrict__ boxes, const float* __restrict__ mean3,
-                                                          const float* __restrict__ std3, T* __restrict__ out, int Tn,
-                                                          int Hs, int Ws, int V, int Sh, int Sw) {
+__device__ __forceinline__ void resample_band(const unsigned char* __restrict__ fbase, const int* __restrict__ boxes,
+                                              const float* __restrict__ mean3, const float* __restrict__ std3,
+                                              T* __restrict__ out, int Tn, int Hs, int Ws, int Sh, int Sw) {
     extern __shared__ __align__(16) unsigned char smem[];
     int* xsrc_s = reinterpret_cast<int*>(smem);        // [Sw] first tap as a column of the source FRAME
     int* xcnt_s = xsrc_s + Sw;                         // [Sw]
@@ -124,7 +130,6 @@ __global__ __launch_bounds__(kBlock) void k_clip_resample(const unsigned char* _
     }
     __syncthreads();
 
-    const unsigned char* fbase = frames + ((long long)(oc / V) * Tn + t) * Hs * (long long)Ws * 3;
     T* obase = out + (((long long)oc * Tn + t) * 3 * Sh + row0) * (long long)Sw;
     const long long plane = (long long)Sh * Sw;
 
@@ -206,6 +211,59 @@ __global__ __launch_bounds__(kBlock) void k_clip_resample(const unsigned char* _
 }
 
 template <typename T>
+__global__ __launch_bounds__(kBlock) void k_clip_resample(const unsigned char* __restrict__ frames,
+                                                          const int* __restrict__ boxes, const float* __restrict__ mean3,
+                                                          const float* __restrict__ std3, T* __restrict__ out, int Tn,
+                                                          int Hs, int Ws, int V, int Sh, int Sw) {
+    const int t = blockIdx.y, oc = blockIdx.z;
+    resample_band<T>(frames + ((long long)(oc / V) * Tn + t) * Hs * (long long)Ws * 3, boxes, mean3, std3, out, Tn, Hs, Ws,
+                     Sh, Sw);
+}
+
+// The same pass over a packed arena of videos of different sizes.  clips [B][4] int64: (byte offset of the video's first
+// frame, Hs, Ws, F), its F frames back to back, rows Ws * 3 bytes apart, any alignment.  frame_idx [B * V][Tn] int32: the
+// stored frame output frame t of output clip oc shows, clamped into [0, F - 1].  Sizes, offset and indices are device data
+// the launcher cannot see: a record that does not describe F whole frames inside [arena, arena + arena_bytes) is decided
+// here, from values every lane of the workgroup reads alike, before any byte of the arena is read, and its clip is written
+// as zeros.  A record that passes keeps every read of the body inside its own video: the body clamps rows into [0, Hs) and
+// column runs into [0, Ws).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_clip_resample_ragged(const unsigned char* __restrict__ arena, long long arena_bytes,
+                                                                 const long long* __restrict__ clips,
+                                                                 const int* __restrict__ frame_idx,
+                                                                 const int* __restrict__ boxes, const float* __restrict__ mean3,
+                                                                 const float* __restrict__ std3, T* __restrict__ out, int Tn,
+                                                                 int V, int Sh, int Sw) {
+    const int band = blockIdx.x, t = blockIdx.y, oc = blockIdx.z;
+    const long long* rec = clips + (long long)(oc / V) * 4;
+    const long long off = rec[0], hs = rec[1], ws = rec[2], nf = rec[3];
+    // read beside the record, not after the verdict: the table has a row per output clip whatever the records say, and
+    // one wait covers both loads
+    int fraw = frame_idx[(long long)oc * Tn + t];
+    int touch = boxes[(long long)oc * 9];                          // the body's box reads then hit the scalar cache
+    asm volatile("" : "+s"(fraw), "+s"(touch));                    // keeps both loads here: the compiler would sink them below the verdict
+    long long f = fraw;
+    bool ok = hs >= 1 && hs <= kMaxSide && ws >= 1 && ws <= kMaxSide && nf >= 1 && off >= 0 && off <= arena_bytes;
+    const long long fbytes = ok ? hs * ws * 3 : 3;                 // at most 3 * 2^28 once the sides passed
+    // off + nf * fbytes <= arena_bytes without a 64-bit division: nf <= room bounds nf below 2^63, the high half of the
+    // 128-bit product says whether the low half is all of it
+    const unsigned long long room = (unsigned long long)arena_bytes - (unsigned long long)off;   // meaningful once ok
+    if (ok) ok = (unsigned long long)nf <= room && __umul64hi((unsigned long long)nf, (unsigned long long)fbytes) == 0 &&
+                 (unsigned long long)nf * (unsigned long long)fbytes <= room;
+    if (!ok) {
+        const int row0 = band * kBandRows;
+        const int rows_here = (Sh - row0) < kBandRows ? (Sh - row0) : kBandRows;
+        T* obase = out + (((long long)oc * Tn + t) * 3 * Sh + row0) * (long long)Sw;
+        const long long plane = (long long)Sh * Sw;
+        for (int c = 0; c < 3; ++c)
+            for (int i = threadIdx.x; i < rows_here * Sw; i += kBlock) st(obase + c * plane + i, 0.0f);
+        return;
+    }
+    f = f < 0 ? 0 : (f > nf - 1 ? nf - 1 : f);
+    resample_band<T>(arena + off + f * fbytes, boxes, mean3, std3, out, Tn, (int)hs, (int)ws, Sh, Sw);
+}
+
+template <typename T>
 int resample_impl(const unsigned char* frames, const int* boxes, const float* mean3, const float* std3, void* out, int B,
                   int Tn, int Hs, int Ws, int V, int Sh, int Sw, rk_stream_t stream) {
     if (!frames || !boxes || !mean3 || !std3 || !out) return RK_ERR_NULL_POINTER;
@@ -221,6 +279,23 @@ int resample_impl(const unsigned char* frames, const int* boxes, const float* me
     return launch_status();
 }
 
+template <typename T>
+int resample_ragged_impl(const unsigned char* arena, long long arena_bytes, const long long* clips, const int* frame_idx,
+                         const int* boxes, const float* mean3, const float* std3, void* out, int B, int V, int Tn, int Sh,
+                         int Sw, rk_stream_t stream) {
+    if (!arena || !clips || !frame_idx || !boxes || !mean3 || !std3 || !out) return RK_ERR_NULL_POINTER;
+    if (arena_bytes <= 0 || B <= 0 || V <= 0 || Tn <= 0 || Sh <= 0 || Sw <= 0) return RK_ERR_BAD_DIMS;
+    if ((long long)B * V > 65535 || Tn > 65535) return RK_ERR_BAD_DIMS;                                      // grid.z, grid.y
+    const size_t lds = resample_lds_bytes(Sw);                     // the source sizes do not enter: Sw alone, as above
+    static DynLdsRaised raised;
+    const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_clip_resample_ragged<T>), lds, raised);
+    if (rc != RK_OK) return rc;
+    const dim3 grid((unsigned)((Sh + kBandRows - 1) / kBandRows), (unsigned)Tn, (unsigned)(B * V));
+    hipLaunchKernelGGL((k_clip_resample_ragged<T>), grid, dim3(kBlock), lds, (hipStream_t)stream, arena, arena_bytes, clips,
+                       frame_idx, boxes, mean3, std3, (T*)out, Tn, V, Sh, Sw);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -232,6 +307,18 @@ int rk_clip_resample_u8_f32(const unsigned char* frames, const int* boxes, const
 int rk_clip_resample_u8_bf16(const unsigned char* frames, const int* boxes, const float* mean3, const float* std3, void* out,
                              int B, int T, int Hs, int Ws, int V, int Sh, int Sw, rk_stream_t stream) {
     return resample_impl<__hip_bfloat16>(frames, boxes, mean3, std3, out, B, T, Hs, Ws, V, Sh, Sw, stream);
+}
+
+int rk_clip_resample_ragged_u8_f32(const unsigned char* arena, long long arena_bytes, const long long* clips,
+                                   const int* frame_idx, const int* boxes, const float* mean3, const float* std3, float* out,
+                                   int B, int V, int T, int Sh, int Sw, rk_stream_t stream) {
+    return resample_ragged_impl<float>(arena, arena_bytes, clips, frame_idx, boxes, mean3, std3, out, B, V, T, Sh, Sw, stream);
+}
+int rk_clip_resample_ragged_u8_bf16(const unsigned char* arena, long long arena_bytes, const long long* clips,
+                                    const int* frame_idx, const int* boxes, const float* mean3, const float* std3, void* out,
+                                    int B, int V, int T, int Sh, int Sw, rk_stream_t stream) {
+    return resample_ragged_impl<__hip_bfloat16>(arena, arena_bytes, clips, frame_idx, boxes, mean3, std3, out, B, V, T, Sh, Sw,
+                                                stream);
 }
 
 }  // extern "C"
