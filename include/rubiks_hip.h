@@ -712,6 +712,67 @@ int rk_clip_resample_ragged_u8_bf16(const unsigned char* arena, long long arena_
                                     const int* frame_idx, const int* boxes, const float* mean3, const float* std3,
                                     void* out, int B, int V, int T, int Sh, int Sw, rk_stream_t stream);
 
+/* ---- baseline JPEG frames decoded on the device, bit-exact to libjpeg(-turbo)'s defaults (rk_jpeg.hip) ----
+ * What Pillow's Image.open(f).convert("RGB") gives for a baseline file: Huffman decode, jidctint's ISLOW IDCT with its
+ * range limit, fancy (triangle) chroma upsampling, jdcolor's 16-bit fixed-point YCbCr -> RGB.  The host parses the
+ * headers (rubiksnet_amd.jpeg.parse_jpeg) and hands the device the entropy-coded segments and the tables.
+ * Supported: SOF0, 8-bit, one interleaved scan, grayscale or YCbCr at 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2), any Huffman
+ * tables, DRI / RSTn, width and height in [1, 16384].
+ *   streams  device bytes, any alignment: the entropy-coded segments (byte stuffing and RSTn markers included, the
+ *            marker that ends the scan excluded) of all frames
+ *   frames   device [n] records, below           qtabs  device [nq, 64] in NATURAL (row-major) order
+ *   htabs    device [nh] decoding tables, below  rgb    device bytes: frame i's [H, W, 3] at its rgb_off (pack_clips' layout)
+ *   status   device int [n + 1]: a RK_JPEG_* code per frame, [n] = the number of frames whose code is not 0
+ * Everything but n, nq, nh and the byte counts is device data the launcher cannot check.  The kernels bound every loop
+ * by counts from the record, never read outside [streams, streams + stream_bytes), qtabs, htabs or the workspace and
+ * never write outside a frame's H * W * 3 bytes or the workspace, whatever the tables and the stream hold; bits wanted
+ * past a frame's segment or past a marker read as zero.  A record is checked from its own fields before the first read
+ * (RK_JPEG_BAD_RECORD: a size outside [1, 16384], components not 1 or 3, an unknown sampling, a table index >= nq / nh,
+ * a negative offset, stream_off + stream_len > stream_bytes, rgb_off + H * W * 3 > rgb_bytes, or a workspace too small
+ * for the frames up to and including this one).  A frame with a non-zero code is written as zeros (where its rgb range
+ * is valid).  The decoder is stricter than libjpeg, which conceals errors: a code no table holds, a run past
+ * coefficient 63 (a ZRL that no coefficient of the block can follow included), a DC difference above 11 bits, an AC value above 10 bits, a DC value outside [-2047, 2047], bits
+ * wanted past the end, a missing or out-of-order RSTn, whole bytes left over, or pad bits that are not ones all fail
+ * the frame.  Five launches on `stream`, ordered by the stream alone; no allocation, no host synchronisation, no
+ * atomics; capturable.  n at most 65535, nq and nh at most 65535.  Returns RK_ERR_NULL_POINTER, RK_ERR_BAD_DIMS (a
+ * count out of range, a negative byte count), RK_ERR_WORKSPACE (NULL, not 16-byte aligned, or too small for the offset
+ * table of n frames) before anything is launched.                                                                  */
+enum {
+    RK_JPEG_OK = 0,
+    RK_JPEG_BAD_RECORD = 1,   /* decided from the record alone */
+    RK_JPEG_BAD_CODE = 2,     /* bits that are no code of the table */
+    RK_JPEG_BAD_RUN = 3,      /* a zero run past coefficient 63 */
+    RK_JPEG_TRUNCATED = 4,    /* bits wanted past the segment's end or past a marker */
+    RK_JPEG_BAD_RESTART = 5,  /* RSTn missing or out of order */
+    RK_JPEG_TRAILING = 6,     /* whole bytes left over, or pad bits that are not ones */
+    RK_JPEG_BAD_VALUE = 7     /* a magnitude category or DC value outside what 8-bit baseline can hold */
+};
+#define RK_JPEG_MAX_SIDE 16384
+typedef struct rk_jpeg_frame {
+    long long stream_off;           /* the frame's entropy-coded segment: bytes [stream_off, stream_off + stream_len) */
+    long long stream_len;
+    long long rgb_off;              /* byte offset of its [height, width, 3] output in rgb */
+    int width, height;
+    int components;                 /* 1 (grayscale: R = G = B = Y) or 3 (YCbCr) */
+    int sampling;                   /* 0: 4:4:4, 1: 4:2:2 (luma 2x1), 2: 4:2:0 (luma 2x2); ignored for 1 component */
+    int restart_interval;           /* MCUs between RSTn markers, 0: none */
+    unsigned short quant[3];        /* per component: row of qtabs */
+    unsigned short dc[3], ac[3];    /* per component: element of htabs */
+    unsigned short reserved;
+} rk_jpeg_frame;                    /* 64 bytes */
+typedef struct rk_jpeg_huff {
+    unsigned short look[512];       /* the next 9 bits -> (length << 8) | symbol for a code of 1..9 bits, else 0 */
+    int maxcode[18];                /* [l], l = 1..16: the largest code of l bits, -1 when there is none */
+    int valoff[18];                 /* [l]: index in huffval of the first code of l bits, minus that code */
+    unsigned char huffval[256];
+} rk_jpeg_huff;                     /* 1424 bytes */
+/* Workspace for the n records of a HOST copy of the table (quantised coefficients and component planes of every frame
+ * whose sizes are valid, behind an offset table); 0 for n < 1 or a NULL table. */
+size_t rk_jpeg_workspace_bytes(const rk_jpeg_frame* frames_host, int n);
+int rk_jpeg_decode_u8(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                      const unsigned short* qtabs, const rk_jpeg_huff* htabs, int nq, int nh, int n, unsigned char* rgb,
+                      long long rgb_bytes, void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream);
+
 /* ---- squeeze-and-excitation gate of RubiksNet-Small -- widening row f3 of SURVEY 8(f) --------------
  * SELayer (rubiksnet/backbone.py:56-71): y = x * sigmoid(W2 relu(W1 mean_hw(x))).  x, y, dy, dx [F, C, P];
  * mean / gate / dgate [F, C] f32.  squeeze: mean over P; scale: y = x * gate; scale_backward: dx = dy * gate and

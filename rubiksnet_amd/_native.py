@@ -159,6 +159,10 @@ SIGNATURES["rk_optim_step_ext_f32"] = (_i, [_i, _p, _i, _i, _p, _i, _p, _i, ctyp
 SIGNATURES["rk_metrics_state_bytes"] = (_sz, [_i, _i])
 for _sfx in ("f32", "bf16", "f16"):
     SIGNATURES["rk_metrics_update_" + _sfx] = (_i, [_p, _p, _p] + [_i] * 9 + [_p] * 5)
+# baseline JPEG decode (rk_jpeg.hip): host frame table, n -> bytes; streams, stream_bytes, frames, qtabs, htabs, nq, nh, n,
+# rgb, rgb_bytes, workspace, workspace_bytes, status, stream
+SIGNATURES["rk_jpeg_workspace_bytes"] = (_sz, [_p, _i])
+SIGNATURES["rk_jpeg_decode_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _p, ctypes.c_longlong, _p, _sz, _p, _p])
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw

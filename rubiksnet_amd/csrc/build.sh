@@ -21,7 +21,7 @@ stale() {   # $1 = unit: true when its object is missing or older than the sourc
 }
 objs=()
 pids=()
-for src in rk_misc rk3d rk3d_16 rk3d_slab rk2d rk_tshift rk_bn rk_pw rk_pw2 rk_pw3 rk_pw4 rk_pw16 rk_pw16_odd rk_stem16 rk_clip rk_resample rk_optim rk_metrics; do
+for src in rk_misc rk3d rk3d_16 rk3d_slab rk2d rk_tshift rk_bn rk_pw rk_pw2 rk_pw3 rk_pw4 rk_pw16 rk_pw16_odd rk_stem16 rk_clip rk_resample rk_optim rk_metrics rk_jpeg; do
   objs+=("$here/$src.o")
   if [[ "${RK_INCREMENTAL:-0}" == "1" ]] && ! stale "$src"; then continue; fi
   rm -f "$here/$src.o"

@@ -1,0 +1,417 @@
+// rk_jpeg_core.hpp -- the baseline JPEG decode core of rk_jpeg.hip as plain host/device C++: record check and
+// geometry, bit reader, Huffman step, one scan's entropy decode, jidctint's ISLOW IDCT, fancy upsampling and
+// YCbCr -> RGB.  The kernels only distribute this code over lanes; tests/jpeg_core_main.cpp compiles the same text for
+// the CPU under AddressSanitizer / UBSan, which is the bounds proof for the kernels' logic.
+//
+// Every function is bounded by counts from the record and reads the stream through a source object that the caller
+// bounds; arithmetic that a hostile stream could overflow is done in unsigned (two's complement wrap, as the hardware).
+#pragma once
+#include <stdint.h>
+
+#include "rubiks_hip.h"
+
+#if defined(__HIPCC__)
+#define RKJ_HD __host__ __device__ __forceinline__
+#else
+#define RKJ_HD inline
+#endif
+
+namespace rkjpeg {
+
+// zigzag position -> natural (row-major) position
+RKJ_HD int natural_of(int k) {
+    static constexpr unsigned char t[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    return t[k & 63];
+}
+
+// ------------------------------------------------------------------------------------------------ geometry
+struct Geometry {
+    int ncomp;              // 1 or 3
+    int hs, vs;             // luma blocks per MCU, horizontally and vertically (1 or 2)
+    int mcux, mcuy;         // MCUs per row / column
+    int bpm;                // blocks per MCU
+    int cw, ch;             // the REAL chroma size: ceil(W / hs), ceil(H / vs) (what the upsampler may look at)
+    int yw, yh;             // luma plane size (whole MCUs)
+    int pcw, pch;           // chroma plane size (whole MCUs)
+    long long nblocks;      // blocks of the frame
+    long long coef_bytes;   // nblocks * 64 shorts
+    long long plane_off[3]; // byte offsets of the planes behind the coefficients
+    long long bytes;        // coefficients + planes, rounded up to 16
+};
+
+// Sizes from the record's own fields; false when a field is outside the supported class.
+RKJ_HD bool geometry(const rk_jpeg_frame& f, Geometry& g) {
+    if (f.width < 1 || f.width > RK_JPEG_MAX_SIDE || f.height < 1 || f.height > RK_JPEG_MAX_SIDE) return false;
+    if (f.components != 1 && f.components != 3) return false;
+    if (f.components == 3 && (f.sampling < 0 || f.sampling > 2)) return false;
+    g.ncomp = f.components;
+    g.hs = (f.components == 3 && f.sampling >= 1) ? 2 : 1;
+    g.vs = (f.components == 3 && f.sampling == 2) ? 2 : 1;
+    g.mcux = (f.width + 8 * g.hs - 1) / (8 * g.hs);
+    g.mcuy = (f.height + 8 * g.vs - 1) / (8 * g.vs);
+    g.bpm = g.ncomp == 1 ? 1 : g.hs * g.vs + 2;
+    g.cw = (f.width + g.hs - 1) / g.hs;
+    g.ch = (f.height + g.vs - 1) / g.vs;
+    g.yw = g.mcux * 8 * g.hs;
+    g.yh = g.mcuy * 8 * g.vs;
+    g.pcw = g.mcux * 8;
+    g.pch = g.mcuy * 8;
+    g.nblocks = (long long)g.mcux * g.mcuy * g.bpm;
+    g.coef_bytes = g.nblocks * 128;
+    g.plane_off[0] = g.coef_bytes;
+    g.plane_off[1] = g.plane_off[0] + (long long)g.yw * g.yh;
+    g.plane_off[2] = g.plane_off[1] + (long long)g.pcw * g.pch;
+    const long long end = g.ncomp == 1 ? g.plane_off[1] : g.plane_off[2] + (long long)g.pcw * g.pch;
+    g.bytes = (end + 15) & ~15LL;
+    return true;
+}
+
+// Workspace bytes of one record: 0 when its sizes are not valid (such a frame is never decoded).
+RKJ_HD long long frame_workspace_bytes(const rk_jpeg_frame& f) {
+    Geometry g;
+    return geometry(f, g) ? g.bytes : 0;
+}
+
+// Bytes of the offset table that heads the workspace: n + 1 int64, rounded up to 16.
+RKJ_HD long long offset_table_bytes(int n) { return (((long long)n + 1) * 8 + 15) & ~15LL; }
+
+// May the frame's H * W * 3 bytes be written?  (asked even of a record that is otherwise invalid: it is zeroed then)
+RKJ_HD bool rgb_range_ok(const rk_jpeg_frame& f, long long rgb_bytes) {
+    if (f.width < 1 || f.width > RK_JPEG_MAX_SIDE || f.height < 1 || f.height > RK_JPEG_MAX_SIDE) return false;
+    const long long need = (long long)f.width * f.height * 3;
+    return f.rgb_off >= 0 && f.rgb_off <= rgb_bytes && need <= rgb_bytes - f.rgb_off;
+}
+
+// The record alone: RK_JPEG_OK or RK_JPEG_BAD_RECORD.  ws_begin / ws_end: the frame's region of the workspace.
+RKJ_HD int check_record(const rk_jpeg_frame& f, long long stream_bytes, long long rgb_bytes, int nq, int nh,
+                        long long ws_end, long long workspace_bytes) {
+    Geometry g;
+    if (!geometry(f, g)) return RK_JPEG_BAD_RECORD;
+    if (!rgb_range_ok(f, rgb_bytes)) return RK_JPEG_BAD_RECORD;
+    if (f.stream_off < 0 || f.stream_len < 0 || f.stream_off > stream_bytes || f.stream_len > stream_bytes - f.stream_off)
+        return RK_JPEG_BAD_RECORD;
+    if (f.restart_interval < 0 || f.restart_interval > 65535) return RK_JPEG_BAD_RECORD;
+    for (int c = 0; c < g.ncomp; ++c)
+        if (f.quant[c] >= nq || f.dc[c] >= nh || f.ac[c] >= nh) return RK_JPEG_BAD_RECORD;
+    if (ws_end > workspace_bytes) return RK_JPEG_BAD_RECORD;
+    return RK_JPEG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ bits
+// Src: `int byte(long long pos)` for 0 <= pos < len, the byte at that position of the frame's segment.
+// The reader never asks for a position outside [0, len).  Bits past the end or past a marker read as zero and are
+// counted (`fake`): a decoder that used one has run off the data.
+template <class Src>
+struct BitReader {
+    Src& src;
+    long long pos, len;
+    unsigned acc;           // the next bits, most significant first
+    int bits;               // valid bits in acc
+    int fake;               // how many of them are zeros that stand for missing data
+    bool stopped;           // a marker or the end was reached: nothing more is read
+
+    RKJ_HD BitReader(Src& s, long long n) : src(s), pos(0), len(n), acc(0), bits(0), fake(0), stopped(false) {}
+
+    RKJ_HD bool at_stop() {
+        if (pos >= len) return true;
+        if (src.byte(pos) != 0xFF) return false;
+        return pos + 1 >= len || src.byte(pos + 1) != 0x00;
+    }
+    RKJ_HD void fill() {    // at least 25 bits afterwards; at most 4 rounds
+        while (bits <= 24) {
+            unsigned b = 0;
+            if (!stopped) {
+                if (pos >= len) {
+                    stopped = true;
+                } else {
+                    b = (unsigned)src.byte(pos) & 0xFFu;
+                    if (b != 0xFF) {
+                        pos += 1;
+                    } else if (pos + 1 < len && src.byte(pos + 1) == 0x00) {
+                        pos += 2;                       // FF 00 is the data byte FF
+                    } else {
+                        stopped = true;                 // a marker (or a lone FF at the end): not consumed
+                        b = 0;
+                    }
+                }
+            }
+            if (stopped) fake += 8;
+            acc |= b << (24 - bits);
+            bits += 8;
+        }
+    }
+    RKJ_HD unsigned peek(int n) const { return acc >> (32 - n); }       // 1 <= n <= 25, after fill()
+    RKJ_HD void drop(int n) { acc <<= n; bits -= n; }
+    RKJ_HD bool overrun() const { return bits < fake; }                   // a fake bit was consumed
+
+    // The end of an entropy-coded interval: less than a byte of real bits left, all ones, and a marker or the end next.
+    RKJ_HD int end_interval() {
+        if (overrun()) return RK_JPEG_TRUNCATED;
+        const int real = bits - fake;
+        if (real >= 8) return RK_JPEG_TRAILING;
+        if (real > 0 && peek(real) != (1u << real) - 1u) return RK_JPEG_TRAILING;
+        if (!stopped && !at_stop()) return RK_JPEG_TRAILING;
+        return RK_JPEG_OK;
+    }
+    // Between two intervals: the marker must be RSTn with n == expected; the reader starts afresh behind it.
+    RKJ_HD int restart(int expected) {
+        const int rc = end_interval();
+        if (rc != RK_JPEG_OK) return rc;
+        if (pos + 1 >= len || src.byte(pos) != 0xFF || src.byte(pos + 1) != 0xD0 + (expected & 7)) return RK_JPEG_BAD_RESTART;
+        pos += 2;
+        acc = 0;
+        bits = fake = 0;
+        stopped = false;
+        return RK_JPEG_OK;
+    }
+    RKJ_HD int finish() {
+        const int rc = end_interval();
+        if (rc != RK_JPEG_OK) return rc;
+        return pos >= len ? RK_JPEG_OK : RK_JPEG_TRAILING;              // a marker inside the segment: data left over
+    }
+};
+
+// One Huffman symbol, or -1 when the bits are no code.  Every index is masked: the table is untrusted device data.
+template <class Src>
+RKJ_HD int huff_symbol(BitReader<Src>& br, const rk_jpeg_huff& h) {
+    br.fill();
+    const unsigned e = h.look[br.peek(9) & 511];
+    const int l = (int)(e >> 8);
+    if (l >= 1 && l <= 9) {
+        br.drop(l);
+        return (int)(e & 255);
+    }
+    for (int n = 10; n <= 16; ++n) {
+        const int code = (int)br.peek(n);
+        if (code <= h.maxcode[n]) {
+            br.drop(n);
+            return h.huffval[(unsigned)(code + h.valoff[n]) & 255];
+        }
+    }
+    return -1;
+}
+
+// s bits as a JPEG signed magnitude (1 <= s <= 15)
+template <class Src>
+RKJ_HD int receive_extend(BitReader<Src>& br, int s) {
+    br.fill();
+    const int v = (int)br.peek(s);
+    br.drop(s);
+    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+// ------------------------------------------------------------------------------------------------ one scan
+// Sink: put(zigzag_position, value) for the non-zero coefficients of the current block (the sink maps the position to
+// natural order: natural_of, or its inverse once per lane -- a table lookup per coefficient here would be a global
+// memory round trip on the device), end_block(block_index) after each; the blocks come in scan order (MCU by MCU; in an MCU the luma blocks row by row, then Cb, then Cr).
+// tabs: the frame's six tables, DC of component c at [c], AC at [3 + c].
+// Returns a RK_JPEG_* code; on an error the blocks from the failing one on have not been written.
+template <class Src, class Sink>
+RKJ_HD int decode_scan(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, Sink& sink) {
+    BitReader<Src> br(src, f.stream_len);
+    const int nluma = g.ncomp == 1 ? 1 : g.hs * g.vs;
+    const long long nmcu = (long long)g.mcux * g.mcuy;
+    int pred0 = 0, pred1 = 0, pred2 = 0;                    // scalars, not an array: a lane-private array indexed by c lives in scratch memory
+    int next_rst = 0, until_rst = f.restart_interval;
+    long long block = 0;
+    for (long long m = 0; m < nmcu; ++m) {
+        if (f.restart_interval > 0) {
+            if (until_rst == 0) {
+                const int rc = br.restart(next_rst);
+                if (rc != RK_JPEG_OK) return rc;
+                next_rst = (next_rst + 1) & 7;
+                until_rst = f.restart_interval;
+                pred0 = pred1 = pred2 = 0;
+            }
+            --until_rst;
+        }
+        for (int j = 0; j < g.bpm; ++j, ++block) {
+            const int c = j < nluma ? 0 : j - nluma + 1;
+            int s = huff_symbol(br, tabs[c]);
+            if (s < 0) return RK_JPEG_BAD_CODE;
+            if (s > 11) return RK_JPEG_BAD_VALUE;
+            int dcv = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
+            if (s) dcv += receive_extend(br, s);
+            if (dcv < -2047 || dcv > 2047) return RK_JPEG_BAD_VALUE;
+            pred0 = c == 0 ? dcv : pred0;
+            pred1 = c == 1 ? dcv : pred1;
+            pred2 = c == 2 ? dcv : pred2;
+            if (dcv) sink.put(0, dcv);
+            int k = 1;
+            for (int guard = 0; guard < 63 && k < 64; ++guard) {        // at most 63 symbols a block
+                const int rs = huff_symbol(br, tabs[3 + c]);
+                if (rs < 0) return RK_JPEG_BAD_CODE;
+                const int r = rs >> 4;
+                s = rs & 15;
+                if (s == 0) {
+                    if (r != 15) break;                                 // EOB
+                    k += 16;                                            // ZRL: a coefficient of this block must follow
+                    if (k > 63) return RK_JPEG_BAD_RUN;
+                    continue;
+                }
+                k += r;
+                if (k > 63) return RK_JPEG_BAD_RUN;
+                if (s > 10) return RK_JPEG_BAD_VALUE;
+                sink.put(k, receive_extend(br, s));
+                ++k;
+            }
+            if (br.overrun()) return RK_JPEG_TRUNCATED;
+            sink.end_block(block);
+        }
+    }
+    return br.finish();
+}
+
+// ------------------------------------------------------------------------------------------------ IDCT
+// libjpeg's jidctint.c (jpeg_idct_islow), 8-bit samples: CONST_BITS 13, PASS1_BITS 2, dequantisation by multiplication,
+// the all-zero-AC column shortcut, the masked range limit.  out: 8 rows of 8 samples, `stride` bytes apart.
+RKJ_HD unsigned idct_descale(unsigned x, int n) { return (unsigned)((int)(x + (1u << (n - 1))) >> n); }
+RKJ_HD unsigned char idct_limit(unsigned x) {
+    // range_limit[(x & 1023) + 128]: the 10-bit field read as signed, plus 128, clamped to a sample
+    const int s = (int)((x & 1023u) ^ 512u) - 512 + 128;
+    return (unsigned char)(s < 0 ? 0 : (s > 255 ? 255 : s));
+}
+
+RKJ_HD void idct_islow(const short* coef, const unsigned short* q, unsigned char* out, long long stride) {
+    typedef unsigned U;
+    constexpr U F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299,
+                F1_847 = 15137, F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
+    U ws[64];
+#define RKJ_IDCT_BODY(I0, I1, I2, I3, I4, I5, I6, I7)                                                  \
+    U z2 = I2, z3 = I6;                                                                                \
+    U z1 = (z2 + z3) * F0_541;                                                                         \
+    U tmp2 = z1 - z3 * F1_847;                                                                         \
+    U tmp3 = z1 + z2 * F0_765;                                                                         \
+    z2 = I0;                                                                                           \
+    z3 = I4;                                                                                           \
+    U tmp0 = (z2 + z3) << 13;                                                                          \
+    U tmp1 = (z2 - z3) << 13;                                                                          \
+    const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;        \
+    tmp0 = I7;                                                                                         \
+    tmp1 = I5;                                                                                         \
+    tmp2 = I3;                                                                                         \
+    tmp3 = I1;                                                                                         \
+    z1 = tmp0 + tmp3;                                                                                  \
+    z2 = tmp1 + tmp2;                                                                                  \
+    z3 = tmp0 + tmp2;                                                                                  \
+    U z4 = tmp1 + tmp3;                                                                                \
+    const U z5 = (z3 + z4) * F1_175;                                                                   \
+    tmp0 *= F0_298;                                                                                    \
+    tmp1 *= F2_053;                                                                                    \
+    tmp2 *= F3_072;                                                                                    \
+    tmp3 *= F1_501;                                                                                    \
+    z1 *= 0u - F0_899;                                                                                 \
+    z2 *= 0u - F2_562;                                                                                 \
+    z3 *= 0u - F1_961;                                                                                 \
+    z4 *= 0u - F0_390;                                                                                 \
+    z3 += z5;                                                                                          \
+    z4 += z5;                                                                                          \
+    tmp0 += z1 + z3;                                                                                   \
+    tmp1 += z2 + z4;                                                                                   \
+    tmp2 += z2 + z3;                                                                                   \
+    tmp3 += z1 + z4;
+#define RKJ_DQ(r) ((U)(int)coef[(r) * 8 + c] * (U)q[(r) * 8 + c])
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        if ((coef[8 + c] | coef[16 + c] | coef[24 + c] | coef[32 + c] | coef[40 + c] | coef[48 + c] | coef[56 + c]) == 0) {
+            const U dcval = RKJ_DQ(0) << 2;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) ws[r * 8 + c] = dcval;
+            continue;
+        }
+        RKJ_IDCT_BODY(RKJ_DQ(0), RKJ_DQ(1), RKJ_DQ(2), RKJ_DQ(3), RKJ_DQ(4), RKJ_DQ(5), RKJ_DQ(6), RKJ_DQ(7))
+        ws[0 * 8 + c] = idct_descale(tmp10 + tmp3, 11);
+        ws[7 * 8 + c] = idct_descale(tmp10 - tmp3, 11);
+        ws[1 * 8 + c] = idct_descale(tmp11 + tmp2, 11);
+        ws[6 * 8 + c] = idct_descale(tmp11 - tmp2, 11);
+        ws[2 * 8 + c] = idct_descale(tmp12 + tmp1, 11);
+        ws[5 * 8 + c] = idct_descale(tmp12 - tmp1, 11);
+        ws[3 * 8 + c] = idct_descale(tmp13 + tmp0, 11);
+        ws[4 * 8 + c] = idct_descale(tmp13 - tmp0, 11);
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const U* w = ws + r * 8;
+        unsigned char* o = out + r * stride;
+        RKJ_IDCT_BODY(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7])
+        o[0] = idct_limit(idct_descale(tmp10 + tmp3, 18));
+        o[7] = idct_limit(idct_descale(tmp10 - tmp3, 18));
+        o[1] = idct_limit(idct_descale(tmp11 + tmp2, 18));
+        o[6] = idct_limit(idct_descale(tmp11 - tmp2, 18));
+        o[2] = idct_limit(idct_descale(tmp12 + tmp1, 18));
+        o[5] = idct_limit(idct_descale(tmp12 - tmp1, 18));
+        o[3] = idct_limit(idct_descale(tmp13 + tmp0, 18));
+        o[4] = idct_limit(idct_descale(tmp13 - tmp0, 18));
+    }
+#undef RKJ_DQ
+#undef RKJ_IDCT_BODY
+}
+
+// Where block `b` (scan order) of the frame goes: component and the byte offset of its top-left sample in that
+// component's plane; *stride = the plane's row pitch.
+RKJ_HD void block_place(const Geometry& g, long long b, int* comp, long long* offset, int* stride) {
+    const long long m = b / g.bpm;
+    const int j = (int)(b % g.bpm);
+    const int my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
+    const int nluma = g.ncomp == 1 ? 1 : g.hs * g.vs;
+    if (j < nluma) {
+        const int by = my * g.vs + j / g.hs, bx = mx * g.hs + j % g.hs;
+        *comp = 0;
+        *stride = g.yw;
+        *offset = (long long)by * 8 * g.yw + bx * 8;
+    } else {
+        *comp = j - nluma + 1;
+        *stride = g.pcw;
+        *offset = (long long)my * 8 * g.pcw + mx * 8;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ upsampling and colour
+// One chroma sample at output pixel (x, y) as libjpeg's jdsample.c gives it.  plane: the component's plane, pitch pcw;
+// only columns < cw and rows < ch are looked at (the real samples; what partial MCUs decode beyond them is padding).
+//   4:4:4                     the sample itself
+//   cw <= 2                   box replication (libjpeg takes the plain upsamplers for such narrow components)
+//   4:2:2  h2v1_fancy         even x: (3 s[i] + s[i-1] + 1) >> 2, odd x: (3 s[i] + s[i+1] + 2) >> 2
+//   4:2:0  h2v2_fancy         column sums 3 near + far row, then even x: (3 t + l + 8) >> 4, odd x: (3 t + r + 7) >> 4
+// with an edge column standing in for its missing neighbour, row -1 = row 0 and row ch = row ch - 1.
+RKJ_HD int chroma_at(const unsigned char* plane, const Geometry& g, int x, int y) {
+    if (g.hs == 1) return plane[(long long)y * g.pcw + x];
+    const int i = x >> 1;
+    if (g.cw <= 2) return plane[(long long)(g.vs == 2 ? y >> 1 : y) * g.pcw + i];
+    const int nb = (x & 1) ? (i + 1 < g.cw ? i + 1 : i) : (i > 0 ? i - 1 : i);
+    if (g.vs == 1) {
+        const unsigned char* row = plane + (long long)y * g.pcw;
+        return (3 * row[i] + row[nb] + ((x & 1) ? 2 : 1)) >> 2;
+    }
+    const int r = y >> 1;
+    const int far = (y & 1) ? (r + 1 < g.ch ? r + 1 : r) : (r > 0 ? r - 1 : r);
+    const unsigned char* near_row = plane + (long long)r * g.pcw;
+    const unsigned char* far_row = plane + (long long)far * g.pcw;
+    const int t = 3 * near_row[i] + far_row[i];
+    const int n = 3 * near_row[nb] + far_row[nb];
+    return (3 * t + n + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+RKJ_HD unsigned char clamp_u8(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// jdcolor.c's tables as arithmetic: SCALEBITS 16, FIX(x) = (int)(x * 65536 + 0.5), arithmetic right shifts.
+RKJ_HD void ycc_to_rgb(int y, int cb, int cr, unsigned char* rgb) {
+    const int u = cb - 128, v = cr - 128;
+    rgb[0] = clamp_u8(y + ((91881 * v + 32768) >> 16));
+    rgb[1] = clamp_u8(y + ((-22554 * u - 46802 * v + 32768) >> 16));
+    rgb[2] = clamp_u8(y + ((116130 * u + 32768) >> 16));
+}
+
+// The RGB of output pixel (x, y) from the frame's planes (`base`: the frame's workspace region).
+RKJ_HD void pixel_rgb(const unsigned char* base, const Geometry& g, int x, int y, unsigned char* rgb) {
+    const int luma = base[g.plane_off[0] + (long long)y * g.yw + x];
+    if (g.ncomp == 1) {
+        rgb[0] = rgb[1] = rgb[2] = (unsigned char)luma;
+        return;
+    }
+    ycc_to_rgb(luma, chroma_at(base + g.plane_off[1], g, x, y), chroma_at(base + g.plane_off[2], g, x, y), rgb);
+}
+
+}  // namespace rkjpeg

@@ -11,6 +11,8 @@ device does the rest in one launch (augment.ragged_u8_to_clips, rk_clip_resample
   return_dataset    the five values of dataset/config.py, as a table
   pack_clips        the collate function: arena [bytes], clips int64 [B, 4], labels
   FrameLoader       DataLoader workers -> pinned staging arena -> side-stream copy + ragged launch
+                    (decode="device": the workers ship the JPEG files' bytes, jpeg.pack_jpeg_clips packs them and
+                    rk_jpeg_decode_u8 decodes them on the side stream in front of the ragged launch)
   DeviceFrameCache  a small set decoded once and resident in HBM; only the three small tables travel per batch
 
 The random draws come from a `torch.Generator` (or torch's global generator, which a DataLoader seeds per worker): the
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 import torch.utils.data as data
 
-from . import augment
+from . import augment, jpeg
 from .input_pipeline import IMAGENET_MEAN, IMAGENET_STD, _mean_std_on, _near_gpu
 
 __all__ = ["segment_indices", "VideoRecord", "RubiksDataset", "InMemoryVideos", "return_dataset", "pack_clips",
@@ -161,11 +163,18 @@ class RubiksDataset(_Sampled):
     """The reference's RubiksDataset (core.py:11-87, :267-325) with its constructor arguments.  With a `transform` a
     sample is `(transform(list of PIL images), label)` as there; with `transform=None` it is `(uint8 [K, H, W, 3], label)`,
     the decoded frames for the device path.  `generator`: a torch.Generator for the draws; None uses torch's global
-    generator, which a DataLoader seeds differently in every worker."""
+    generator, which a DataLoader seeds differently in every worker.  decode="device" (with transform=None): a sample is
+    `(list of frames, label)`, a frame being the bytes of its file, undecoded, for jpeg.pack_jpeg_clips and the device
+    decoder -- or uint8 [H, W, 3] decoded here as ever where jpeg.parse_jpeg refuses the file."""
 
     def __init__(self, root_path, list_file, num_segments=3, new_length=1, image_tmpl="img_{:05d}.jpg", transform=None,
                  random_shift=True, test_mode=False, remove_missing=False, dense_sample=False, all_sample=False,
-                 twice_sample=False, only_even_indices=True, logger=None, generator=None):
+                 twice_sample=False, only_even_indices=True, logger=None, generator=None, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
+        if decode == "device" and transform is not None:
+            raise ValueError("decode='device' hands out undecoded files: it goes with transform=None")
+        self.decode = decode
         if image_tmpl == "{:06d}-{}_{:05d}.jpg":
             raise NotImplementedError("the %r naming (halved frame counts, core.py:84-86) is not supported" % image_tmpl)
         self.verbose = logger is not None
@@ -197,6 +206,18 @@ class RubiksDataset(_Sampled):
             with Image.open(self._path(directory, 2)) as im:
                 return [im.convert("RGB")]
 
+    def _load_bytes(self, directory, idx):
+        """A frame for the device decoder: the file's bytes; decoded here (uint8 [H, W, 3]) where the file is missing,
+        unreadable or outside what the device decodes -- by _load_image, with its stand-in rule."""
+        try:
+            with open(self._path(directory, idx), "rb") as fh:
+                raw = fh.read()
+            if jpeg.parse_jpeg(raw) is not None:
+                return raw
+        except OSError:
+            pass
+        return np.asarray(self._load_image(directory, idx)[0], dtype=np.uint8)
+
     def __getitem__(self, index):
         record = self.video_list[index]
         first = self._path(record.path, 2 if self.only_even_indices else 1)
@@ -205,6 +226,9 @@ class RubiksDataset(_Sampled):
         return self.get(record, self.sample(record.num_frames))
 
     def get(self, record, indices):
+        if self.decode == "device":
+            numbers = _frame_numbers(indices, record.num_frames, self.new_length)
+            return [self._load_bytes(record.path, p) for p in numbers], record.label
         images = []
         for p in _frame_numbers(indices, record.num_frames, self.new_length):
             images.extend(self._load_image(record.path, p))
@@ -362,15 +386,29 @@ class FrameLoader(_Feeder):
     `views` spatial crops per video come from `box_fn((H, W), generator)` -> int32 [views, 9]; default: a multiscale crop
     + flip for split "train", the centre crop otherwise.  With a twice_sample test dataset the 2T decoded frames become
     two temporal clips through frame_idx; rows are crop-major, temporal clip minor, so
-    `clips.view(B, -1, size, size)` is what evaluation.fold_views(..., views=loader.views) takes."""
+    `clips.view(B, -1, size, size)` is what evaluation.fold_views(..., views=loader.views) takes.
+
+    decode="device" (with a RubiksDataset(..., decode="device")): the workers read the files and pack their bytes
+    (jpeg.pack_jpeg_clips); the compressed arena and its tables travel through the same pinned slot, rk_jpeg_decode_u8
+    decodes them into a per-slot RGB arena on the side stream, and the unchanged ragged launch follows on that arena.
+    Boxes are drawn from the sizes in the headers, so nothing waits for the device; the clips are bit-identical to the
+    host path's.  `fallback_frames` counts the frames that travelled decoded (files the device does not decode);
+    `decode_errors()` reads, on request, how many frames the device refused (they come out as zero frames)."""
 
     def __init__(self, dataset, batch, split, device="cuda:0", dtype=torch.float32, size=224, views=1, box_fn=None,
-                 num_workers=0, depth=2, seed=0, temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5):
+                 num_workers=0, depth=2, seed=0, temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5,
+                 decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
+        if getattr(dataset, "decode", "host") != decode:
+            raise ValueError("the dataset hands out %s-decoded samples, the loader was asked for decode=%r"
+                             % (getattr(dataset, "decode", "host"), decode))
         self._init_feeder(dataset, batch, split, device, dtype, size, views, box_fn, temporal_clips, seed, flip_p)
         self.depth = int(depth)
+        self.decode, self.fallback_frames = decode, 0
         shuffle = (split == "train") if shuffle is None else shuffle
         self._dl = data.DataLoader(dataset, batch_size=self.batch, shuffle=shuffle, num_workers=num_workers,
-                                   collate_fn=pack_clips, drop_last=drop_last,
+                                   collate_fn=pack_clips if decode == "host" else jpeg.pack_jpeg_clips, drop_last=drop_last,
                                    generator=torch.Generator().manual_seed(seed + 1), persistent_workers=num_workers > 0)
         self._stream = torch.cuda.Stream(self.device)
         self._pinned = [None] * self.depth                 # staging arenas, host
@@ -381,6 +419,12 @@ class FrameLoader(_Feeder):
         self._consumed = [torch.cuda.Event() for _ in range(self.depth)]
         self._copied = [None] * self.depth
         self._host = [None] * self.depth
+        if decode == "device":
+            self._rgb = [None] * self.depth                # decoded frames, device
+            self._ws = [None] * self.depth                 # the decoder's workspace, device
+            self._status = [None] * self.depth             # its per-frame codes, device
+            with torch.cuda.stream(self._stream):
+                self._errors = torch.zeros((), dtype=torch.int64, device=self.device)
         _mean_std_on(self.device, IMAGENET_MEAN, IMAGENET_STD)      # the one blocking upload happens here, not per batch
         for ev in self._consumed:
             ev.record(torch.cuda.current_stream(self.device))
@@ -403,8 +447,83 @@ class FrameLoader(_Feeder):
             tab = self._tab[slot] = (host, dev)
         return tab
 
+    def decode_errors(self):
+        """Frames the device decoder refused so far (each came out as a zero frame).  Waits for the side stream: ask
+        once, at the end of an epoch."""
+        if self.decode != "device":
+            return 0
+        self._stream.synchronize()
+        return int(self._errors.item())
+
+    @staticmethod
+    def _grown(t, need, make):
+        """t if it holds `need` elements, else a new tensor with headroom (batches of a ragged set differ in size)."""
+        return t if t is not None and t.numel() >= need else make(need + need // 4)
+
+    def _launch_jpeg(self, slot, packed):
+        """_launch for a jpeg.PackedJpeg: the blob and the host-decoded frames are staged, the decode launch fills the
+        slot's RGB arena, the host-decoded frames are copied into their places, the ragged launch follows."""
+        clips, labels, rgb_bytes = packed.clips, packed.labels, int(packed.rgb_bytes)
+        n, V = clips.shape[0], self.views
+        sizes = [(int(h), int(w)) for h, w in clips[:, 1:3].tolist()]
+        frame_idx = torch.cat([_temporal_index(int(k), self.temporal_clips, self.crops) for k in clips[:, 3].tolist()])
+        boxes = self._boxes(sizes)
+        B, T = augment.check_ragged(rgb_bytes, clips, frame_idx, boxes, self.size, V)
+        blob_bytes = nbytes = packed.blob.numel()
+        spots = []                                          # (offset in the staging arena, offset in the RGB arena, bytes)
+        for off, frame in packed.fallback:
+            nbytes = (nbytes + 15) & ~15
+            spots.append((nbytes, int(off), frame.numel()))
+            nbytes += frame.numel()
+        nj = int(packed.layout[0])
+        if self._copied[slot] is not None:
+            self._copied[slot].synchronize()                # as in _launch: the copies that last read this slot are done
+        if self._pinned[slot] is None or self._pinned[slot].numel() < nbytes:
+            cap = nbytes + nbytes // 4
+            with _near_gpu(self.device):
+                self._pinned[slot] = torch.empty(cap, dtype=torch.uint8).pin_memory()
+            with torch.cuda.stream(self._stream):
+                self._arena[slot] = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        with torch.cuda.stream(self._stream):
+            self._rgb[slot] = self._grown(self._rgb[slot], rgb_bytes,
+                                          lambda m: torch.empty(m, dtype=torch.uint8, device=self.device))
+            self._ws[slot] = self._grown(self._ws[slot], int(packed.workspace_bytes),
+                                         lambda m: torch.empty(m, dtype=torch.uint8, device=self.device))
+            self._status[slot] = self._grown(self._status[slot], nj + 1,
+                                             lambda m: torch.zeros(m, dtype=torch.int32, device=self.device))
+        host, dev = self._tables_for(slot, n, T)
+        self._pinned[slot][:blob_bytes].copy_(packed.blob)
+        for (at, _, m), (_, frame) in zip(spots, packed.fallback):
+            self._pinned[slot][at:at + m].copy_(frame.reshape(-1))
+        for name, t in (("clips", clips), ("frame_idx", frame_idx), ("boxes", boxes), ("labels", labels)):
+            host[name][:t.shape[0]].copy_(t)
+        self._host[slot] = {"packed": packed, "clips": clips, "frame_idx": frame_idx, "boxes": boxes, "labels": labels}
+        self.fallback_frames += len(packed.fallback)
+        with torch.cuda.stream(self._stream):
+            self._stream.wait_event(self._consumed[slot])
+            self._arena[slot][:nbytes].copy_(self._pinned[slot][:nbytes], non_blocking=True)
+            for name in host:
+                dev[name].copy_(host[name], non_blocking=True)
+            if self._copied[slot] is None:
+                self._copied[slot] = torch.cuda.Event()
+            self._copied[slot].record(self._stream)
+            rgb = self._rgb[slot][:rgb_bytes]
+            if nj:
+                (frames, htabs, qtabs, streams), (_, nh, nq) = jpeg.sections(self._arena[slot], packed.layout)
+                status = self._status[slot][:nj + 1]
+                jpeg.launch_decode(streams, frames, qtabs, htabs, nj, rgb, self._ws[slot], status, nq, nh)
+                self._errors += status[nj]
+            for at, off, m in spots:
+                rgb[off:off + m].copy_(self._arena[slot][at:at + m])
+            augment.ragged_u8_to_clips(rgb, dev["clips"][:n], dev["frame_idx"][:n * V], dev["boxes"][:n * V], self.size,
+                                       views=V, dtype=self.dtype, out=self._out[slot][:n * V])
+            self._ready[slot].record(self._stream)
+        return n
+
     def _launch(self, slot, packed):
         """Stage one packed batch into `slot` and queue its copies and the kernel on the side stream."""
+        if self.decode == "device":
+            return self._launch_jpeg(slot, packed)
         arena, clips, labels = packed
         n, nbytes, V = clips.shape[0], arena.numel(), self.views
         sizes = [(int(h), int(w)) for h, w in clips[:, 1:3].tolist()]

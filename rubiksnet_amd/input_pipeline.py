@@ -9,7 +9,8 @@ clips (1 byte per element over PCIe) and `stacked_u8_to_clips` does transpose + 
 
 `SyntheticClipLoader` is the benchmark's feeder: random uint8 clips in pinned host memory, copied on a side HIP
 stream and transformed there, double buffered, so the copy and the transform of batch i+1 overlap the step on
-batch i.  (Dataset indexing, JPEG decoding and the PIL crops stay out of scope)
+batch i.  (Dataset indexing, the PIL crops and JPEG decoding were out of scope here; they live in dataset.py,
+augment.py and jpeg.py now.)
 """
 import os
 

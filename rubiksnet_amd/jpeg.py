@@ -1,0 +1,379 @@
+"""Baseline JPEG frames decoded on the device (rk_jpeg_decode_u8, csrc/rk_jpeg.hip), bit-exact to what Pillow's
+`Image.open(f).convert("RGB")` gives with libjpeg(-turbo)'s defaults.
+
+A DataLoader worker only reads the files and walks their headers; the file bytes travel instead of decoded frames
+(about an eighth of the bytes), and the GPU does the Huffman decode, the IDCT, the upsampling and the colour conversion.
+
+  parse_jpeg          marker walk over one file: a JpegHeader for SOF0 / 8-bit / one interleaved scan / grayscale or YCbCr
+                      at 4:4:4, 4:2:2, 4:2:0; None for anything else; never raises
+  pack_jpeg_clips     the collate function, twin of dataset.pack_clips: entropy-coded segments back to back, a record per
+                      frame, de-duplicated quantisation / Huffman tables, and the `clips` table pack_clips would have made
+                      of the decoded frames.  A frame parse_jpeg rejects is decoded here with Pillow and travels as RGB.
+  launch_decode       the launch on device tensors
+  decode_jpeg_frames  upload + launch for one packed batch
+
+There is no CPU path: a missing library is an error (tests compare with Pillow).
+"""
+import collections
+import io
+
+import numpy as np
+import torch
+
+__all__ = ["JpegHeader", "parse_jpeg", "pack_jpeg_clips", "PackedJpeg", "decode_jpeg_frames", "launch_decode",
+           "workspace_bytes_for", "huffman_record", "FRAME_DTYPE", "HUFF_DTYPE", "STATUS_NAMES", "MAX_SIDE"]
+
+MAX_SIDE = 16384
+STATUS_NAMES = ("ok", "bad record", "bad code", "run past 63", "truncated", "bad restart", "trailing data", "bad value")
+
+# include/rubiks_hip.h: rk_jpeg_frame (64 bytes) and rk_jpeg_huff (1424 bytes)
+FRAME_DTYPE = np.dtype({"names": ["stream_off", "stream_len", "rgb_off", "width", "height", "components", "sampling",
+                                  "restart_interval", "quant", "dc", "ac", "reserved"],
+                        "formats": ["<i8", "<i8", "<i8", "<i4", "<i4", "<i4", "<i4", "<i4", ("<u2", 3), ("<u2", 3), ("<u2", 3),
+                                    "<u2"],
+                        "offsets": [0, 8, 16, 24, 28, 32, 36, 40, 44, 50, 56, 62], "itemsize": 64})
+HUFF_DTYPE = np.dtype([("look", "<u2", 512), ("maxcode", "<i4", 18), ("valoff", "<i4", 18), ("huffval", "u1", 256)])
+assert FRAME_DTYPE.itemsize == 64 and HUFF_DTYPE.itemsize == 1424
+
+_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                    21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53,
+                    60, 61, 54, 47, 55, 62, 63])
+_SAMPLING = {0x11: 0, 0x21: 1, 0x22: 2}            # luma H/V factors -> sampling class (chroma 1x1)
+
+
+class JpegHeader:
+    """What the device needs of one file.  width, height; components 1 or 3; sampling 0 (4:4:4), 1 (4:2:2), 2 (4:2:0);
+    restart_interval; per component: quant (uint16 [64], natural order), dc / ac ((counts uint8 [16], values bytes));
+    scan: the (start, end) byte range of the entropy-coded segment in the file."""
+    __slots__ = ("width", "height", "components", "sampling", "restart_interval", "quant", "dc", "ac", "scan")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def _scan_end(arr, start):
+    """The entropy-coded segment runs to the first FF that is followed by anything but 00 (a stuffed FF) or D0..D7
+    (RSTn) -- or to the end of the data, where a file was cut."""
+    body = arr[start:]
+    ff = np.flatnonzero(body[:-1] == 0xFF)
+    if ff.size:
+        nxt = body[ff + 1]
+        stop = ff[(nxt != 0) & ((nxt < 0xD0) | (nxt > 0xD7))]
+        if stop.size:
+            return start + int(stop[0])
+    return arr.size
+
+
+def _parse(data):
+    arr = np.frombuffer(data, dtype=np.uint8)
+    size = arr.size
+    if size < 4 or arr[0] != 0xFF or arr[1] != 0xD8:
+        return None
+    qt, dc, ac = {}, {}, {}
+    frame, restart, jfif, pos = None, 0, False, 2
+    while True:
+        if pos + 4 > size or arr[pos] != 0xFF:
+            return None
+        m = int(arr[pos + 1])
+        if m == 0xFF:                                   # a fill byte in front of a marker
+            pos += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD7:              # stand-alone markers carry no length
+            pos += 2
+            continue
+        if m in (0xD8, 0xD9):
+            return None
+        n = (int(arr[pos + 2]) << 8) | int(arr[pos + 3])
+        seg, end = pos + 4, pos + 2 + n
+        if n < 2 or end > size:
+            return None
+        if m == 0xDB:                                   # DQT
+            p = seg
+            while p < end:
+                if p + 65 > end or arr[p] >> 4:         # 16-bit tables belong to 12-bit files
+                    return None
+                tab = np.zeros(64, dtype=np.uint16)
+                tab[_ZIGZAG] = arr[p + 1:p + 65]
+                qt[int(arr[p]) & 15] = tab
+                p += 65
+        elif m == 0xC4:                                 # DHT
+            p = seg
+            while p < end:
+                if p + 17 > end:
+                    return None
+                tc, th = int(arr[p]) >> 4, int(arr[p]) & 15
+                counts = arr[p + 1:p + 17]
+                nval = int(counts.sum())
+                if tc > 1 or th > 3 or nval > 256 or p + 17 + nval > end:
+                    return None
+                (ac if tc else dc)[th] = (counts.copy(), arr[p + 17:p + 17 + nval].tobytes())
+                p += 17 + nval
+        elif m == 0xC0:                                 # SOF0
+            if frame is not None or n < 8:
+                return None
+            prec, h, w, nf = int(arr[seg]), (int(arr[seg + 1]) << 8) | int(arr[seg + 2]), \
+                (int(arr[seg + 3]) << 8) | int(arr[seg + 4]), int(arr[seg + 5])
+            if prec != 8 or nf not in (1, 3) or n != 8 + 3 * nf or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+                return None
+            frame = (w, h, [(int(arr[seg + 6 + 3 * i]), int(arr[seg + 7 + 3 * i]), int(arr[seg + 8 + 3 * i])) for i in range(nf)])
+        elif 0xC1 <= m <= 0xCF:                         # every other SOFn, arithmetic conditioning, JPG
+            return None
+        elif m == 0xDD:                                 # DRI
+            if n != 4:
+                return None
+            restart = (int(arr[seg]) << 8) | int(arr[seg + 1])
+        elif m == 0xE0:
+            jfif = jfif or arr[seg:seg + 5].tobytes() == b"JFIF\0"
+        elif m == 0xEE:
+            if arr[seg:seg + 5].tobytes() == b"Adobe":  # Adobe's transform flag: RGB, CMYK or YCCK data
+                return None
+        elif m == 0xDC:                                 # DNL
+            return None
+        elif m == 0xDA:                                 # SOS
+            if frame is None:
+                return None
+            w, h, comps = frame
+            ns = int(arr[seg])
+            if ns != len(comps) or n != 6 + 2 * ns:
+                return None
+            sel = [(int(arr[seg + 1 + 2 * i]), int(arr[seg + 2 + 2 * i])) for i in range(ns)]
+            if [c for c, _ in sel] != [c for c, _, _ in comps]:
+                return None
+            if (int(arr[seg + 1 + 2 * ns]), int(arr[seg + 2 + 2 * ns]), int(arr[seg + 3 + 2 * ns])) != (0, 63, 0):
+                return None
+            if ns == 1:
+                if comps[0][1] != 0x11:
+                    return None
+                sampling = 0
+            else:
+                if comps[1][1] != 0x11 or comps[2][1] != 0x11 or comps[0][1] not in _SAMPLING:
+                    return None
+                if not jfif and [c for c, _, _ in comps] != [1, 2, 3]:      # libjpeg would guess the colour space
+                    return None
+                sampling = _SAMPLING[comps[0][1]]
+            try:
+                quant = [qt[tq] for _, _, tq in comps]
+                dcs = [dc[t >> 4] for _, t in sel]
+                acs = [ac[t & 15] for _, t in sel]
+            except KeyError:
+                return None
+            for counts, _ in dcs + acs:
+                if not _counts_fit(counts):
+                    return None
+            return JpegHeader(width=w, height=h, components=ns, sampling=sampling, restart_interval=restart, quant=quant,
+                              dc=dcs, ac=acs, scan=(end, _scan_end(arr, end)))
+        pos = end
+
+
+def _counts_fit(counts):
+    """Do the code counts per length describe a prefix code (no length holds more codes than are left)?"""
+    code = 0
+    for l in range(16):
+        code += int(counts[l])
+        if code > (1 << (l + 1)):
+            return False
+        code <<= 1
+    return True
+
+
+def parse_jpeg(data):
+    """A JpegHeader for a file the device decodes, None for anything else (progressive, arithmetic, 12-bit, CMYK / Adobe,
+    other samplings, several scans' worth of components, garbage).  Never raises."""
+    try:
+        return _parse(data)
+    except Exception:
+        return None
+
+
+# ------------------------------------------------------------------------------------------------- tables
+def huffman_record(counts, values):
+    """The rk_jpeg_huff record (HUFF_DTYPE scalar array) of a DHT table: counts uint8 [16], values bytes."""
+    rec = np.zeros((), dtype=HUFF_DTYPE)
+    look, maxcode, valoff, huffval = rec["look"], rec["maxcode"], rec["valoff"], rec["huffval"]
+    vals = np.frombuffer(values, dtype=np.uint8)
+    huffval[:vals.size] = vals
+    maxcode[:] = -1
+    code, p = 0, 0
+    for l in range(1, 17):
+        cnt = int(counts[l - 1])
+        if cnt:
+            valoff[l] = p - code
+            if l <= 9:
+                for k in range(cnt):
+                    lo = (code + k) << (9 - l)
+                    look[lo:lo + (1 << (9 - l))] = (l << 8) | int(vals[p + k])
+            code += cnt
+            p += cnt
+            maxcode[l] = code - 1
+        code <<= 1
+    maxcode[17] = 0x7fffffff
+    return rec
+
+
+def workspace_bytes_for(frames):
+    """rk_jpeg_workspace_bytes of a FRAME_DTYPE array, in numpy (a DataLoader worker does not load the HIP library)."""
+    frames = np.asarray(frames)
+    total = ((frames.size + 1) * 8 + 15) & ~15
+    for f in frames.reshape(-1):
+        w, h, nc, s = int(f["width"]), int(f["height"]), int(f["components"]), int(f["sampling"])
+        if not (1 <= w <= MAX_SIDE and 1 <= h <= MAX_SIDE) or nc not in (1, 3) or (nc == 3 and not 0 <= s <= 2):
+            continue
+        hs, vs = (2 if nc == 3 and s >= 1 else 1), (2 if nc == 3 and s == 2 else 1)
+        mx, my = (w + 8 * hs - 1) // (8 * hs), (h + 8 * vs - 1) // (8 * vs)
+        blocks = mx * my * (1 if nc == 1 else hs * vs + 2)
+        planes = mx * my * 64 * (1 if nc == 1 else hs * vs + 2)
+        total += (blocks * 128 + planes + 15) & ~15
+    return total
+
+
+# ------------------------------------------------------------------------------------------------- collate
+PackedJpeg = collections.namedtuple("PackedJpeg", [
+    "blob",             # uint8: frame records | Huffman records | quantisation tables | streams, each section 16-byte aligned
+    "layout",           # int64 [8]: n, nh, nq, offsets of the four sections in blob, stream_bytes
+    "clips",            # int64 [B, 4]: what pack_clips gives for the decoded frames (offset in the RGB arena, H, W, K)
+    "labels",           # int64 [B]
+    "rgb_bytes",        # bytes of the RGB arena
+    "workspace_bytes",  # rk_jpeg_workspace_bytes of the frame table
+    "fallback",         # [(offset in the RGB arena, uint8 [H, W, 3])]: frames decoded on the host
+])
+
+
+def _host_rgb(item):
+    from PIL import Image
+    with Image.open(io.BytesIO(item)) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def _align16(v):
+    return (v + 15) & ~15
+
+
+def pack_jpeg_clips(samples):
+    """The collate function of the device-decode path.  samples: [(frames, label)], `frames` a list whose items are the
+    bytes of a JPEG file, or uint8 [H, W, 3] (a frame the dataset already decoded on the host); all frames of a sample
+    have one size, sizes and frame counts differ freely between samples.  Returns a PackedJpeg.  A file parse_jpeg
+    rejects is decoded here with Pillow and travels as RGB (`fallback`); its place in the RGB arena is reserved like
+    any other frame's."""
+    records, segments, fallback, rows, labels = [], [], [], [], []
+    qindex, hindex, qtabs, htabs = {}, {}, [], []
+
+    def table(index, store, key, build):
+        i = index.get(key)
+        if i is None:
+            i = index[key] = len(store)
+            store.append(build())
+        return i
+
+    rgb_off = stream_off = 0
+    for frames, label in samples:
+        if len(frames) < 1:
+            raise ValueError("a sample without frames")
+        size, first = None, rgb_off
+        for item in frames:
+            head = parse_jpeg(item) if isinstance(item, (bytes, bytearray, memoryview)) else None
+            if head is None:
+                rgb = _host_rgb(item) if isinstance(item, (bytes, bytearray, memoryview)) else np.asarray(item)
+                if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+                    raise ValueError("a frame must be JPEG bytes or uint8 [H, W, 3], got %s %s" % (rgb.dtype, rgb.shape))
+                hw = (rgb.shape[0], rgb.shape[1])
+                fallback.append((rgb_off, torch.from_numpy(np.array(rgb, dtype=np.uint8, order="C"))))
+            else:
+                hw = (head.height, head.width)
+                a, b = head.scan
+                rec = np.zeros((), dtype=FRAME_DTYPE)
+                rec["stream_off"], rec["stream_len"], rec["rgb_off"] = stream_off, b - a, rgb_off
+                rec["width"], rec["height"], rec["components"] = head.width, head.height, head.components
+                rec["sampling"], rec["restart_interval"] = head.sampling, head.restart_interval
+                for c in range(head.components):
+                    q = head.quant[c]
+                    rec["quant"][c] = table(qindex, qtabs, q.tobytes(), lambda: q)
+                    for name, (counts, values) in (("dc", head.dc[c]), ("ac", head.ac[c])):
+                        rec[name][c] = table(hindex, htabs, counts.tobytes() + values,
+                                             lambda: huffman_record(counts, values))
+                records.append(rec)
+                segments.append(np.frombuffer(item, dtype=np.uint8)[a:b])
+                stream_off += b - a
+            if size is None:
+                size = hw
+            elif hw != size:
+                raise ValueError("the frames of one sample differ in size: %r and %r" % (size, hw))
+            rgb_off += hw[0] * hw[1] * 3
+        rows.append((first, size[0], size[1], len(frames)))
+        labels.append(int(label))
+    n, nh, nq = len(records), len(htabs), len(qtabs)
+    if nh > 65535 or nq > 65535:
+        raise ValueError("more than 65535 distinct tables in one batch")
+    frames_arr = np.stack(records) if n else np.zeros(0, dtype=FRAME_DTYPE)
+    o_frames = 0
+    o_huff = _align16(o_frames + n * FRAME_DTYPE.itemsize)
+    o_quant = _align16(o_huff + nh * HUFF_DTYPE.itemsize)
+    o_stream = _align16(o_quant + nq * 128)
+    blob = np.zeros(o_stream + stream_off, dtype=np.uint8)
+    blob[o_frames:o_frames + n * 64] = frames_arr.view(np.uint8).reshape(-1)
+    if nh:
+        blob[o_huff:o_huff + nh * HUFF_DTYPE.itemsize] = np.stack(htabs).view(np.uint8).reshape(-1)
+    if nq:
+        blob[o_quant:o_quant + nq * 128] = np.stack(qtabs).astype("<u2").view(np.uint8).reshape(-1)
+    at = o_stream
+    for seg in segments:
+        blob[at:at + seg.size] = seg
+        at += seg.size
+    layout = torch.tensor([n, nh, nq, o_frames, o_huff, o_quant, o_stream, stream_off], dtype=torch.int64)
+    return PackedJpeg(torch.from_numpy(blob), layout, torch.tensor(rows, dtype=torch.int64).reshape(-1, 4),
+                      torch.tensor(labels, dtype=torch.int64), rgb_off, workspace_bytes_for(frames_arr), fallback)
+
+
+# ------------------------------------------------------------------------------------------------- launch
+def launch_decode(streams, frames, qtabs, htabs, n, rgb, workspace, status, nq=None, nh=None):
+    """rk_jpeg_decode_u8 on the current stream.  Device tensors: streams uint8 [stream_bytes] (any alignment), frames
+    uint8 [n * 64] (rk_jpeg_frame records), qtabs uint8 [nq * 128], htabs uint8 [nh * 1424], rgb uint8 [rgb_bytes],
+    workspace uint8 (16-byte aligned), status int32 [n + 1].  Nothing is allocated and the host does not wait."""
+    from . import _native
+    for name, t in (("streams", streams), ("frames", frames), ("qtabs", qtabs), ("htabs", htabs), ("rgb", rgb),
+                    ("workspace", workspace)):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous uint8 tensor on the GPU" % name)
+    if status.dtype != torch.int32 or not status.is_cuda or status.numel() < n + 1 or not status.is_contiguous():
+        raise ValueError("status must be int32 [n + 1] on the GPU")
+    if frames.numel() < n * FRAME_DTYPE.itemsize:
+        raise ValueError("%d bytes of frame records for n = %d" % (frames.numel(), n))
+    nq = qtabs.numel() // 128 if nq is None else nq
+    nh = htabs.numel() // HUFF_DTYPE.itemsize if nh is None else nh
+    if qtabs.numel() < nq * 128 or htabs.numel() < nh * HUFF_DTYPE.itemsize:
+        raise ValueError("the table arenas are shorter than nq / nh say")
+    with torch.cuda.device(rgb.device):
+        rc = _native.lib().rk_jpeg_decode_u8(
+            streams.data_ptr(), streams.numel(), frames.data_ptr(), qtabs.data_ptr(), htabs.data_ptr(), nq, nh, n,
+            rgb.data_ptr(), rgb.numel(), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
+            torch.cuda.current_stream(rgb.device).cuda_stream)
+    _native.check(rc, "rk_jpeg_decode_u8")
+
+
+def sections(blob, layout):
+    """(frames, htabs, qtabs, streams) views of a PackedJpeg blob (host or device) and (n, nh, nq)."""
+    n, nh, nq, o_frames, o_huff, o_quant, o_stream, stream_bytes = (int(v) for v in layout.tolist())
+    return (blob[o_frames:o_frames + n * 64], blob[o_huff:o_huff + nh * HUFF_DTYPE.itemsize],
+            blob[o_quant:o_quant + nq * 128], blob[o_stream:o_stream + stream_bytes]), (n, nh, nq)
+
+
+def decode_jpeg_frames(packed, device="cuda:0", out=None, workspace=None):
+    """Decode one packed batch on `device` (current stream).  Returns (rgb arena uint8 [rgb_bytes], clips, status int32
+    [n + 1]): the arena and `clips` are what augment.ragged_u8_to_clips takes.  out / workspace: device uint8 tensors to
+    use (at least rgb_bytes / workspace_bytes long).  Frames that travelled as RGB are copied into the arena; status
+    covers the device-decoded frames in order, status[n] counts those that failed (zero frames)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("decode_jpeg_frames decodes on a GPU (no CPU path)")
+    (frames, htabs, qtabs, streams), (n, nh, nq) = sections(packed.blob.to(device), packed.layout)
+    rgb = torch.empty(packed.rgb_bytes, dtype=torch.uint8, device=device) if out is None else out[:packed.rgb_bytes]
+    if rgb.numel() < packed.rgb_bytes:
+        raise ValueError("out holds %d bytes, the batch decodes to %d" % (rgb.numel(), packed.rgb_bytes))
+    status = torch.zeros(n + 1, dtype=torch.int32, device=device)
+    if n:
+        if workspace is None:
+            workspace = torch.empty(packed.workspace_bytes, dtype=torch.uint8, device=device)
+        launch_decode(streams, frames, qtabs, htabs, n, rgb, workspace, status, nq, nh)
+    for off, frame in packed.fallback:
+        rgb[off:off + frame.numel()].copy_(frame.reshape(-1))
+    return rgb, packed.clips, status
