@@ -8,6 +8,8 @@ import ctypes
 import os
 import threading
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RK_HIP_LIB: another build of the same library (kernel A/B runs of tools/; never a different implementation)
 LIB_PATH = os.environ.get("RK_HIP_LIB") or os.path.join(_HERE, "csrc", "librubiks_hip.so")
@@ -216,9 +218,30 @@ def check(rc, what):
         raise RubiksHipError("%s failed: %s (code %d)" % (what, msg, rc))
 
 
-def dtype_suffix(dtype):
-    import torch
+def call(name, *args):
+    """`lib().name(*args)`; a non-zero status raises RubiksHipError naming the entry point."""
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        check(rc, name)
 
+
+def launch(name, dev, *args):
+    """`call` with device `dev` current and its current stream's handle as the last argument."""
+    with torch.cuda.device(dev):
+        call(name, *args, torch.cuda.current_stream(dev).cuda_stream)
+
+
+def ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def workspace(query_name, dev, *dims):
+    """(uint8 scratch tensor on `dev`, its size in bytes as the `*_workspace_bytes` query `query_name` gives it)."""
+    nbytes = int(getattr(lib(), query_name)(*dims))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def dtype_suffix(dtype):
     return {
         torch.float32: "f32",
         torch.float64: "f64",

@@ -20,12 +20,6 @@ from . import _native, config, fin_status
 __all__ = ["AttentionShift", "temporal_shift3", "presoftened"]
 
 
-def _run(name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_native.lib(), name)(*args, torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, name)
-
-
 class _TemporalShift3Func(torch.autograd.Function):
     """y[n,t] = s[c,0] x[n,t-1] + s[c,1] x[n,t] + s[c,2] x[n,t+1], zero padded in t."""
 
@@ -41,8 +35,8 @@ class _TemporalShift3Func(torch.autograd.Function):
         # the ABI takes taps in the compute type: fp64 for f64 tensors, fp32 otherwise
         taps32 = taps.detach().to(torch.float64 if x.dtype == torch.float64 else torch.float32).contiguous()
         y = torch.empty_like(x)
-        _run("rk_tshift3_forward_" + sfx, x.device, x.data_ptr(), taps32.data_ptr(), y.data_ptr(),
-             nt, n_segment, c, h * w)
+        _native.launch("rk_tshift3_forward_" + sfx, x.device, x.data_ptr(), taps32.data_ptr(), y.data_ptr(),
+                       nt, n_segment, c, h * w)
         ctx.save_for_backward(x, taps32)
         ctx.n_segment = n_segment
         ctx.sfx = sfx
@@ -56,12 +50,10 @@ class _TemporalShift3Func(torch.autograd.Function):
         gy = gy.contiguous()
         gx = torch.empty_like(x)
         gtaps = torch.empty_like(taps32)
-        L = _native.lib()
         fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
-        ws_bytes = int(L.rk_tshift3_backward_workspace_bytes(nt, ctx.n_segment, c, h * w))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-        _run("rk_tshift3_backward_" + ctx.sfx, x.device, gy.data_ptr(), x.data_ptr(), taps32.data_ptr(),
-             gx.data_ptr(), gtaps.data_ptr(), nt, ctx.n_segment, c, h * w, ws.data_ptr(), ws_bytes)
+        ws, ws_bytes = _native.workspace("rk_tshift3_backward_workspace_bytes", x.device, nt, ctx.n_segment, c, h * w)
+        _native.launch("rk_tshift3_backward_" + ctx.sfx, x.device, gy.data_ptr(), x.data_ptr(), taps32.data_ptr(),
+                       gx.data_ptr(), gtaps.data_ptr(), nt, ctx.n_segment, c, h * w, ws.data_ptr(), ws_bytes)
         return gx, gtaps.to(ctx.taps_dtype), None
 
 
@@ -74,7 +66,7 @@ class _SoftTapsFunc(torch.autograd.Function):
         w = weight.detach().contiguous()
         t = temperature.detach().to(device=w.device, dtype=torch.float32).reshape(1)
         taps = torch.empty_like(w)
-        _run("rk_soft_taps_forward_f32", w.device, w.data_ptr(), t.data_ptr(), taps.data_ptr(), w.shape[0])
+        _native.launch("rk_soft_taps_forward_f32", w.device, w.data_ptr(), t.data_ptr(), taps.data_ptr(), w.shape[0])
         ctx.save_for_backward(w, t, taps)
         return taps
 
@@ -83,8 +75,8 @@ class _SoftTapsFunc(torch.autograd.Function):
         w, t, taps = ctx.saved_tensors
         gtaps = gtaps.contiguous().float()
         gw = torch.empty_like(w)
-        _run("rk_soft_taps_backward_f32", w.device, w.data_ptr(), t.data_ptr(), taps.data_ptr(), gtaps.data_ptr(),
-             gw.data_ptr(), w.shape[0])
+        _native.launch("rk_soft_taps_backward_f32", w.device, w.data_ptr(), t.data_ptr(), taps.data_ptr(), gtaps.data_ptr(),
+                       gw.data_ptr(), w.shape[0])
         return gw, None
 
 
@@ -99,7 +91,7 @@ class _SoftTapsManyFunc(torch.autograd.Function):
         jobs, offs, total, max_c = plan
         dev = weights[0].device
         taps = torch.empty(total, 3, dtype=torch.float32, device=dev)
-        _run("rk_soft_taps_many_forward_f32", dev, jobs.data_ptr(), len(weights), taps.data_ptr(), max_c)
+        _native.launch("rk_soft_taps_many_forward_f32", dev, jobs.data_ptr(), len(weights), taps.data_ptr(), max_c)
         ctx.plan = plan
         ctx.dev = dev
         ctx.set_materialize_grads(False)                    # a layer that took no part in the graph: None, not zeros
@@ -115,8 +107,8 @@ class _SoftTapsManyFunc(torch.autograd.Function):
             parts.append(torch.zeros(o1 - o, 3, dtype=torch.float32, device=ctx.dev) if g is None else g.float())
         gcat = torch.cat(parts, dim=0).contiguous()
         gw = torch.empty_like(gcat)
-        _run("rk_soft_taps_many_backward_f32", ctx.dev, jobs.data_ptr(), len(gtaps), taps.data_ptr(), gcat.data_ptr(),
-             gw.data_ptr(), max_c)
+        _native.launch("rk_soft_taps_many_backward_f32", ctx.dev, jobs.data_ptr(), len(gtaps), taps.data_ptr(),
+                       gcat.data_ptr(), gw.data_ptr(), max_c)
         return (None,) + tuple(gw[o:o1] if g is not None else None
                                for g, o, o1 in zip(gtaps, offs, list(offs[1:]) + [total]))
 

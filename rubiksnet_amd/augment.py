@@ -191,11 +191,8 @@ def frames_u8_to_clips(frames, boxes, out_hw, views=1, mean=IMAGENET_MEAN, std=I
         raise RuntimeError("out must be a contiguous %s tensor [B * views, T, 3, Sh, Sw] on the frames' device" % dtype)
     ms = _mean_std_on(dev, mean, std)
     if B and T:
-        with torch.cuda.device(dev):
-            rc = getattr(_native.lib(), "rk_clip_resample_u8_" + _SFX[dtype])(
-                frames.data_ptr(), boxes.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr(), out.data_ptr(), B, T, Hs, Ws,
-                views, sh, sw, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_clip_resample_u8")
+        _native.launch("rk_clip_resample_u8_" + _SFX[dtype], dev, frames.data_ptr(), boxes.data_ptr(), ms[0].data_ptr(),
+                       ms[1].data_ptr(), out.data_ptr(), B, T, Hs, Ws, views, sh, sw)
     return out
 
 
@@ -300,11 +297,9 @@ def ragged_u8_to_clips(arena, clips, frame_idx, boxes, out_hw, views=1, mean=IMA
         raise RuntimeError("out must be a contiguous %s tensor [B * views, T, 3, Sh, Sw] on the arena's device" % dtype)
     ms = _mean_std_on(dev, mean, std)
     if B and T:
-        with torch.cuda.device(dev):
-            rc = getattr(_native.lib(), "rk_clip_resample_ragged_u8_" + _SFX[dtype])(
-                arena.data_ptr(), arena.numel(), clips.data_ptr(), frame_idx.data_ptr(), boxes.data_ptr(), ms[0].data_ptr(),
-                ms[1].data_ptr(), out.data_ptr(), B, views, T, sh, sw, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_clip_resample_ragged_u8")
+        _native.launch("rk_clip_resample_ragged_u8_" + _SFX[dtype], dev, arena.data_ptr(), arena.numel(), clips.data_ptr(),
+                       frame_idx.data_ptr(), boxes.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr(), out.data_ptr(), B, views, T,
+                       sh, sw)
     return out
 
 

@@ -50,7 +50,7 @@ class _SEGate(torch.autograd.Function):
         Fr, C, H, W = x.shape
         y = torch.empty_like(x)
         g32 = gate.detach().float().contiguous()
-        _se_call("rk_se_scale_", x, x.data_ptr(), g32.data_ptr(), y.data_ptr(), Fr, C, H * W)
+        _native.launch("rk_se_scale_" + _SE_SFX[x.dtype], x.device, x.data_ptr(), g32.data_ptr(), y.data_ptr(), Fr, C, H * W)
         ctx.save_for_backward(x, g32)
         ctx.gate_dtype = gate.dtype
         return y
@@ -64,8 +64,8 @@ class _SEGate(torch.autograd.Function):
             dy = dy.to(x.dtype)
         dx = torch.empty_like(x)
         dgate = torch.empty_like(g32)
-        _se_call("rk_se_scale_backward_", x, dy.data_ptr(), x.data_ptr(), g32.data_ptr(), dx.data_ptr(), dgate.data_ptr(),
-                 Fr, C, H * W)
+        _native.launch("rk_se_scale_backward_" + _SE_SFX[x.dtype], x.device, dy.data_ptr(), x.data_ptr(), g32.data_ptr(),
+                       dx.data_ptr(), dgate.data_ptr(), Fr, C, H * W)
         return dx, dgate.to(ctx.gate_dtype)
 
 
@@ -76,7 +76,7 @@ class _SESqueeze(torch.autograd.Function):
     def forward(ctx, x):
         Fr, C, H, W = x.shape
         mean = torch.empty(Fr, C, dtype=torch.float32, device=x.device)
-        _se_call("rk_se_squeeze_", x, x.data_ptr(), mean.data_ptr(), Fr, C, H * W)
+        _native.launch("rk_se_squeeze_" + _SE_SFX[x.dtype], x.device, x.data_ptr(), mean.data_ptr(), Fr, C, H * W)
         ctx.shape, ctx.dtype = x.shape, x.dtype
         return mean
 
@@ -87,13 +87,6 @@ class _SESqueeze(torch.autograd.Function):
 
 
 _SE_SFX = {torch.float32: "f32", torch.bfloat16: "bf16"}
-
-
-def _se_call(name, x, *args):
-    dev = x.device
-    with torch.cuda.device(dev):
-        rc = getattr(_native.lib(), name + _SE_SFX[x.dtype])(*args, torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, name)
 
 
 class SELayer(nn.Module):

@@ -57,7 +57,7 @@ def record(device=None):
                     rec = _Record(index)
                     # the zeros must be there before any launch on any stream can report into them (once per device)
                     torch.cuda.current_stream().synchronize()
-                    _native.check(_native.lib().rk_fin_status_register(rec.dev.data_ptr()), "rk_fin_status_register")
+                    _native.call("rk_fin_status_register", rec.dev.data_ptr())
                 _records[index] = rec
     return rec.dev
 

@@ -23,44 +23,39 @@ def fused_bn_enabled():
     return config.switches().fused_bn
 
 
-def _ws(L, Fr, C, P, dev):
-    nbytes = int(L.rk_bn_workspace_bytes(Fr, C, P))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-# ---- tile statistics handed over by the GEMM that produced a tensor (rk_pw_gemm_packed_stats_bf16, round 5) ----
+# ---- tile statistics handed over by the GEMM that produced a tensor (the bf16 GEMM, the fp32 stem and fused blocks) ----
 def attach_stats(t, stats):
-    """`stats` (float4 [C][tiles], one record per 64 columns) describe `t` as it is now."""
+    """`stats` (float4 [C][tiles]) describe `t` as it is now."""
     t._rk_stats = stats
-    t._rk_stats_count = t.numel() // t.shape[1]
+    t._rk_stats_count = t.numel() // t.shape[1]        # elements per channel the tiles add up to
     t._rk_stats_version = t._version          # an in-place edit of the tensor invalidates them
     return t
 
 
-def take_stats(x):
+def take_stats(x, channels=None, count=None):
+    """The tile statistics a producing GEMM attached to `x` (float4 [C][tiles]), if they describe exactly this tensor
+    (`channels`, `count`: what the consumer expects; default: x's own channel count and elements per channel)."""
     st = getattr(x, "_rk_stats", None)
     if st is None:
         return None
-    if (st.dim() != 3 or st.shape[0] != x.shape[1] or st.shape[1] < 1 or st.shape[2] != 4 or st.device != x.device
-            or st.dtype != torch.float32 or getattr(x, "_rk_stats_count", None) != x.numel() // x.shape[1]
+    channels = x.shape[1] if channels is None else channels
+    count = x.numel() // x.shape[1] if count is None else count
+    # (tiles of 128 / 64 columns or a workgroup's column halves, by kernel generation: every tile carries its own count)
+    if (st.dim() != 3 or st.shape[0] != channels or st.shape[1] < 1 or st.shape[2] != 4 or st.device != x.device
+            or st.dtype != torch.float32 or getattr(x, "_rk_stats_count", None) != count
             or getattr(x, "_rk_stats_version", None) != x._version):
         return None
     return st
 
 
-def _finish_tiles(L, stats, count, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev, stream):
-    """Tile records -> rows (mean, invstd, a, b) [+ 4 packed rows]; running statistics / num_batches_tracked as
-    nn.BatchNorm2d's training forward (the same finisher the fp32 fused block uses, train_block._finish)."""
+def _finish_tiles(stats, count, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev, stream):
+    """Tile records -> rows (mean, invstd, a, b), then (a, b, mean, invstd) per channel packed as [C][4] in rows 4-7;
+    running statistics / num_batches_tracked as nn.BatchNorm2d's training forward."""
     C = weight.shape[0]
     out = torch.empty(8, C, dtype=torch.float32, device=dev)
-    _native.check(L.rk_bn_finish_tiles_f32(stats.data_ptr(), stats.shape[1], count, weight.data_ptr(), bias.data_ptr(),
-                                           _ptr(running_mean), _ptr(running_var), out[0].data_ptr(), out[1].data_ptr(),
-                                           out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), C, float(eps),
-                                           float(momentum), counter_ptr, stream), "rk_bn_finish_tiles_f32")
+    _native.call("rk_bn_finish_tiles_f32", stats.data_ptr(), stats.shape[1], count, weight.data_ptr(), bias.data_ptr(),
+                 _native.ptr(running_mean), _native.ptr(running_var), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                 out[3].data_ptr(), out[4].data_ptr(), C, float(eps), float(momentum), counter_ptr, stream)
     return out
 
 
@@ -70,7 +65,6 @@ class _BNReLUTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, with_skip=False, counter_ptr=None,
                 stats=None):
-        L = _native.lib()
         Fr, C, H, W = x.shape
         P = H * W
         dev = x.device
@@ -79,11 +73,10 @@ class _BNReLUTrain(torch.autograd.Function):
             # the producing GEMM already reduced x tile by tile: finish + ONE normalising pass (no statistics pass over x)
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
-                fin = _finish_tiles(L, stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
+                fin = _finish_tiles(stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
                                     stream)
-                _native.check(getattr(L, "rk_bn_apply_affine_" + _SFX[x.dtype])(
-                    x.data_ptr(), fin[2].data_ptr(), fin[3].data_ptr(), y.data_ptr(), Fr, C, P, int(relu), stream),
-                    "rk_bn_apply_affine")
+                _native.call("rk_bn_apply_affine_" + _SFX[x.dtype], x.data_ptr(), fin[2].data_ptr(), fin[3].data_ptr(),
+                             y.data_ptr(), Fr, C, P, int(relu), stream)
             ctx.save_for_backward(x, weight, bias, fin[0], fin[1])
             ctx.relu = relu
             ctx.with_skip = with_skip
@@ -92,14 +85,11 @@ class _BNReLUTrain(torch.autograd.Function):
             return y
         save_mean = torch.empty(C, dtype=torch.float32, device=dev)
         save_invstd = torch.empty(C, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws, nbytes = _ws(L, Fr, C, P, dev)
-            # counter_ptr: address of the module's num_batches_tracked (int64 device scalar), incremented in the launch
-            rc = getattr(L, "rk_bn_relu_forward_counted_" + _SFX[x.dtype])(
-                x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean), _ptr(running_var),
-                save_mean.data_ptr(), save_invstd.data_ptr(), y.data_ptr(), Fr, C, P, float(eps), float(momentum),
-                int(relu), counter_ptr, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_bn_relu_forward")
+        ws, nbytes = _native.workspace("rk_bn_workspace_bytes", dev, Fr, C, P)
+        # counter_ptr: address of the module's num_batches_tracked (int64 device scalar), incremented in the launch
+        _native.launch("rk_bn_relu_forward_counted_" + _SFX[x.dtype], dev, x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                       _native.ptr(running_mean), _native.ptr(running_var), save_mean.data_ptr(), save_invstd.data_ptr(),
+                       y.data_ptr(), Fr, C, P, float(eps), float(momentum), int(relu), counter_ptr, ws.data_ptr(), nbytes)
         ctx.save_for_backward(x, weight, bias, save_mean, save_invstd)
         ctx.relu = relu
         ctx.with_skip = with_skip
@@ -113,7 +103,6 @@ class _BNReLUTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip=None):
         x, weight, bias, save_mean, save_invstd = ctx.saved_tensors
-        L = _native.lib()
         Fr, C, H, W = x.shape
         P = H * W
         dev = x.device
@@ -127,13 +116,10 @@ class _BNReLUTrain(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws, nbytes = _ws(L, Fr, C, P, dev)
-            rc = getattr(L, "rk_bn_relu_backward_" + _SFX[x.dtype])(
-                dy.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), save_mean.data_ptr(),
-                save_invstd.data_ptr(), _ptr(dskip), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), Fr, C, P,
-                int(ctx.relu), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_bn_relu_backward")
+        ws, nbytes = _native.workspace("rk_bn_workspace_bytes", dev, Fr, C, P)
+        _native.launch("rk_bn_relu_backward_" + _SFX[x.dtype], dev, dy.data_ptr(), x.data_ptr(), weight.data_ptr(),
+                       bias.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), _native.ptr(dskip), dx.data_ptr(),
+                       dgamma.data_ptr(), dbeta.data_ptr(), Fr, C, P, int(ctx.relu), ws.data_ptr(), nbytes)
         return dx, dgamma.to(weight.dtype), dbeta.to(bias.dtype), None, None, None, None, None, None, None, None
 
 
@@ -146,7 +132,6 @@ class _BNReLUTShiftTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, taps, running_mean, running_var, momentum, eps, n_segment, counter_ptr, stats=None):
-        L = _native.lib()
         fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
@@ -157,21 +142,19 @@ class _BNReLUTShiftTrain(torch.autograd.Function):
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if stats is not None:          # x came out of a GEMM that reduced it tile by tile: no statistics pass
-                fin = _finish_tiles(L, stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
+                fin = _finish_tiles(stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
                                     stream)
                 save_mean, save_invstd, ab = fin[0], fin[1], fin[2:4]
             else:
                 save_mean = torch.empty(C, dtype=torch.float32, device=dev)
                 save_invstd = torch.empty(C, dtype=torch.float32, device=dev)
                 ab = torch.empty(2, C, dtype=torch.float32, device=dev)
-                ws, nbytes = _ws(L, Fr, C, P, dev)
-                _native.check(getattr(L, "rk_bn_stats_finish_" + sfx)(
-                    x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean), _ptr(running_var), save_mean.data_ptr(),
-                    save_invstd.data_ptr(), ab.data_ptr(), Fr, C, P, float(eps), float(momentum), counter_ptr, ws.data_ptr(),
-                    nbytes, stream), "rk_bn_stats_finish")
-            _native.check(getattr(L, "rk_tshift3_bn_forward_" + sfx)(
-                x.data_ptr(), taps32.data_ptr(), ab.data_ptr(), y.data_ptr(), Fr, n_segment, C, P, stream),
-                "rk_tshift3_bn_forward")
+                ws, nbytes = _native.workspace("rk_bn_workspace_bytes", dev, Fr, C, P)
+                _native.call("rk_bn_stats_finish_" + sfx, x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                             _native.ptr(running_mean), _native.ptr(running_var), save_mean.data_ptr(), save_invstd.data_ptr(),
+                             ab.data_ptr(), Fr, C, P, float(eps), float(momentum), counter_ptr, ws.data_ptr(), nbytes, stream)
+            _native.call("rk_tshift3_bn_forward_" + sfx, x.data_ptr(), taps32.data_ptr(), ab.data_ptr(), y.data_ptr(), Fr,
+                         n_segment, C, P, stream)
         ctx.save_for_backward(x, weight, bias, taps32, save_mean, save_invstd, ab)
         ctx.n_segment = n_segment
         ctx.taps_dtype = taps.dtype
@@ -180,7 +163,6 @@ class _BNReLUTShiftTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, dskip=None):
         x, weight, bias, taps32, save_mean, save_invstd, ab = ctx.saved_tensors
-        L = _native.lib()
         fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
@@ -203,15 +185,12 @@ class _BNReLUTShiftTrain(torch.autograd.Function):
             stream = torch.cuda.current_stream(dev).cuda_stream
             # (BatchNorm's two sums ride as granules next to the tap sums and are finished by the same finalizer waves: no
             # rk_bn_bwd_finish_tiles launch)
-            nb = int(L.rk_tshift3_bn_backward_fin_workspace_bytes(Fr, S, C, P))
-            ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-            _native.check(getattr(L, "rk_tshift3_bn_backward_fin_" + sfx)(
-                gy.data_ptr(), x.data_ptr(), taps32.data_ptr(), ab.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
-                dz.data_ptr(), gtaps.data_ptr(), k12.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), Fr, S, C, P, ws.data_ptr(),
-                nb, stream), "rk_tshift3_bn_backward_fin")
-            _native.check(getattr(L, "rk_bn_bwd_dx_pre_" + sfx)(
-                dz.data_ptr(), x.data_ptr(), weight.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), k12.data_ptr(),
-                _ptr(dskip), dz.data_ptr(), Fr, C, P, stream), "rk_bn_bwd_dx_pre")            # in place: dz -> d(x)
+            ws, nb = _native.workspace("rk_tshift3_bn_backward_fin_workspace_bytes", dev, Fr, S, C, P)
+            _native.call("rk_tshift3_bn_backward_fin_" + sfx, gy.data_ptr(), x.data_ptr(), taps32.data_ptr(), ab.data_ptr(),
+                         save_mean.data_ptr(), save_invstd.data_ptr(), dz.data_ptr(), gtaps.data_ptr(), k12.data_ptr(),
+                         dgamma.data_ptr(), dbeta.data_ptr(), Fr, S, C, P, ws.data_ptr(), nb, stream)
+            _native.call("rk_bn_bwd_dx_pre_" + sfx, dz.data_ptr(), x.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                         save_invstd.data_ptr(), k12.data_ptr(), _native.ptr(dskip), dz.data_ptr(), Fr, C, P, stream)      # in place: dz -> d(x)
         return (dz, dgamma.to(weight.dtype), dbeta.to(bias.dtype), gtaps.to(ctx.taps_dtype), None, None, None, None, None, None,
                 None)
 
@@ -231,7 +210,7 @@ def bn_relu_tshift_skip(bn, shift, x):
     momentum, counter = _count_batch(bn)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    return _BNReLUTShiftTrain.apply(x, bn.weight, bn.bias, shift.soft_taps(), rm, rv, momentum, bn.eps, S, _ptr(counter),
+    return _BNReLUTShiftTrain.apply(x, bn.weight, bn.bias, shift.soft_taps(), rm, rv, momentum, bn.eps, S, _native.ptr(counter),
                                     take_stats(x))
 
 
@@ -245,7 +224,6 @@ class _BNReLUTShiftForkTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, taps, running_mean, running_var, momentum, eps, n_segment, counter_ptr, stats=None):
-        L = _native.lib()
         fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
@@ -257,23 +235,20 @@ class _BNReLUTShiftForkTrain(torch.autograd.Function):
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if stats is not None:
-                fin = _finish_tiles(L, stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
+                fin = _finish_tiles(stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
                                     stream)
                 save_mean, save_invstd, ab = fin[0], fin[1], fin[2:4]
             else:
                 save_mean = torch.empty(C, dtype=torch.float32, device=dev)
                 save_invstd = torch.empty(C, dtype=torch.float32, device=dev)
                 ab = torch.empty(2, C, dtype=torch.float32, device=dev)
-                ws, nbytes = _ws(L, Fr, C, P, dev)
-                _native.check(getattr(L, "rk_bn_stats_finish_" + sfx)(
-                    x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean), _ptr(running_var), save_mean.data_ptr(),
-                    save_invstd.data_ptr(), ab.data_ptr(), Fr, C, P, float(eps), float(momentum), counter_ptr, ws.data_ptr(),
-                    nbytes, stream), "rk_bn_stats_finish")
-            _native.check(getattr(L, "rk_tshift3_bn_forward_" + sfx)(
-                x.data_ptr(), taps32.data_ptr(), ab.data_ptr(), y.data_ptr(), Fr, n_segment, C, P, stream),
-                "rk_tshift3_bn_forward")
-            _native.check(getattr(L, "rk_bn_relu_gather2_" + sfx)(x.data_ptr(), ab.data_ptr(), xs.data_ptr(), Fr, C, H, W, stream),
-                          "rk_bn_relu_gather2")
+                ws, nbytes = _native.workspace("rk_bn_workspace_bytes", dev, Fr, C, P)
+                _native.call("rk_bn_stats_finish_" + sfx, x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                             _native.ptr(running_mean), _native.ptr(running_var), save_mean.data_ptr(), save_invstd.data_ptr(),
+                             ab.data_ptr(), Fr, C, P, float(eps), float(momentum), counter_ptr, ws.data_ptr(), nbytes, stream)
+            _native.call("rk_tshift3_bn_forward_" + sfx, x.data_ptr(), taps32.data_ptr(), ab.data_ptr(), y.data_ptr(), Fr,
+                         n_segment, C, P, stream)
+            _native.call("rk_bn_relu_gather2_" + sfx, x.data_ptr(), ab.data_ptr(), xs.data_ptr(), Fr, C, H, W, stream)
         ctx.save_for_backward(x, weight, bias, taps32, save_mean, save_invstd, ab)
         ctx.n_segment = n_segment
         ctx.taps_dtype = taps.dtype
@@ -282,7 +257,6 @@ class _BNReLUTShiftForkTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, gxs):
         x, weight, bias, taps32, save_mean, save_invstd, ab = ctx.saved_tensors
-        L = _native.lib()
         fin_status.ensure(x.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = x.shape
         P = H * W
@@ -306,15 +280,12 @@ class _BNReLUTShiftForkTrain(torch.autograd.Function):
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            nb = int(L.rk_tshift3_bn_backward_fin_workspace_bytes(Fr, S, C, P))
-            ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-            _native.check(getattr(L, "rk_tshift3_bn_backward_fork_" + sfx)(
-                gy.data_ptr(), x.data_ptr(), taps32.data_ptr(), ab.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
-                gxs.data_ptr(), dz.data_ptr(), gtaps.data_ptr(), k12.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), Fr, S, C, H, W,
-                ws.data_ptr(), nb, stream), "rk_tshift3_bn_backward_fork")
-            _native.check(getattr(L, "rk_bn_bwd_dx_pre_" + sfx)(
-                dz.data_ptr(), x.data_ptr(), weight.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), k12.data_ptr(),
-                None, dz.data_ptr(), Fr, C, P, stream), "rk_bn_bwd_dx_pre")                       # in place: dz -> d(x)
+            ws, nb = _native.workspace("rk_tshift3_bn_backward_fin_workspace_bytes", dev, Fr, S, C, P)
+            _native.call("rk_tshift3_bn_backward_fork_" + sfx, gy.data_ptr(), x.data_ptr(), taps32.data_ptr(), ab.data_ptr(),
+                         save_mean.data_ptr(), save_invstd.data_ptr(), gxs.data_ptr(), dz.data_ptr(), gtaps.data_ptr(),
+                         k12.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), Fr, S, C, H, W, ws.data_ptr(), nb, stream)
+            _native.call("rk_bn_bwd_dx_pre_" + sfx, dz.data_ptr(), x.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                         save_invstd.data_ptr(), k12.data_ptr(), None, dz.data_ptr(), Fr, C, P, stream)      # in place: dz -> d(x)
         return (dz, dgamma.to(weight.dtype), dbeta.to(bias.dtype), gtaps.to(ctx.taps_dtype), None, None, None, None, None, None,
                 None)
 
@@ -336,7 +307,7 @@ def bn_relu_tshift_fork(bn, shift, x):
     momentum, counter = _count_batch(bn)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    return _BNReLUTShiftForkTrain.apply(x, bn.weight, bn.bias, shift.soft_taps(), rm, rv, momentum, bn.eps, S, _ptr(counter),
+    return _BNReLUTShiftForkTrain.apply(x, bn.weight, bn.bias, shift.soft_taps(), rm, rv, momentum, bn.eps, S, _native.ptr(counter),
                                         take_stats(x))
 
 
@@ -351,7 +322,6 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, weight, bias, shift, running_mean, running_var, momentum, eps, counter_ptr, normalize_grad, stats=None,
                 stride=(1, 1), padding=(0, 0)):
-        L = _native.lib()
         fin_status.ensure(z.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = z.shape
         P = H * W
@@ -364,7 +334,7 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
             stream = torch.cuda.current_stream(dev).cuda_stream
             abmi = None
             if stats is not None:
-                fin = _finish_tiles(L, stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
+                fin = _finish_tiles(stats, Fr * P, weight, bias, running_mean, running_var, momentum, eps, counter_ptr, dev,
                                     stream)
                 save_mean, save_invstd, ab = fin[0], fin[1], fin[2:4]
             else:
@@ -372,16 +342,15 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
                 save_invstd = torch.empty(C, dtype=torch.float32, device=dev)
                 ab = torch.empty(2, C, dtype=torch.float32, device=dev)
                 abmi = torch.empty(C, 4, dtype=torch.float32, device=dev)      # (a, b, mean, invstd): what the backward reads
-                ws, nbytes = _ws(L, Fr, C, P, dev)
-                _native.check(getattr(L, "rk_bn_stats_finish_abmi_" + sfx)(
-                    z.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean), _ptr(running_var), save_mean.data_ptr(),
-                    save_invstd.data_ptr(), ab.data_ptr(), abmi.data_ptr(), Fr, C, P, float(eps), float(momentum), counter_ptr,
-                    ws.data_ptr(), nbytes, stream), "rk_bn_stats_finish_abmi")
+                ws, nbytes = _native.workspace("rk_bn_workspace_bytes", dev, Fr, C, P)
+                _native.call("rk_bn_stats_finish_abmi_" + sfx, z.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                             _native.ptr(running_mean), _native.ptr(running_var), save_mean.data_ptr(), save_invstd.data_ptr(),
+                             ab.data_ptr(), abmi.data_ptr(), Fr, C, P, float(eps), float(momentum), counter_ptr, ws.data_ptr(),
+                             nbytes, stream)
             if abmi is None:
                 abmi = torch.stack((ab[0], ab[1], save_mean, save_invstd), dim=1).contiguous()
-            rc = getattr(L, "rk2d_forward_bn_" + _BNReLUShift2DTrain._SHIFT_SFX[z.dtype])(
-                z.data_ptr(), ab.data_ptr(), shift.data_ptr(), y.data_ptr(), Fr, C, H, W, sH, sW, pH, pW, 0, stream)
-        _native.check(rc, "rk2d_forward_bn")
+            _native.call("rk2d_forward_bn_" + _BNReLUShift2DTrain._SHIFT_SFX[z.dtype], z.data_ptr(), ab.data_ptr(),
+                         shift.data_ptr(), y.data_ptr(), Fr, C, H, W, sH, sW, pH, pW, 0, stream)
         ctx.save_for_backward(z, weight, bias, shift, save_mean, save_invstd, ab, abmi)
         ctx.normalize_grad = bool(normalize_grad)
         ctx.geometry = (sH, sW, pH, pW)
@@ -390,7 +359,6 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         z, weight, bias, shift, save_mean, save_invstd, ab, abmi = ctx.saved_tensors
-        L = _native.lib()
         fin_status.ensure(z.device)        # in-launch finalizers below: a give-up lands in the device's record
         Fr, C, H, W = z.shape
         P = H * W
@@ -411,15 +379,12 @@ class _BNReLUShift2DTrain(torch.autograd.Function):
         sH, sW, pH, pW = ctx.geometry
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            nb = int(L.rk2d_backward_bn_workspace_bytes(Fr, C, H, W, sH, sW, pH, pW))
-            ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-            _native.check(getattr(L, "rk2d_backward_bn_" + _BNReLUShift2DTrain._SHIFT_SFX[z.dtype])(
-                gy.data_ptr(), z.data_ptr(), abmi.data_ptr(), shift.data_ptr(), dz.data_ptr(), gshift.data_ptr(), k12.data_ptr(),
-                dgamma.data_ptr(), dbeta.data_ptr(), Fr, C, H, W, sH, sW, pH, pW, int(ctx.normalize_grad), 0, ws.data_ptr(), nb,
-                stream), "rk2d_backward_bn")
-            _native.check(getattr(L, "rk_bn_bwd_dx_pre_" + sfx)(
-                dz.data_ptr(), z.data_ptr(), weight.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), k12.data_ptr(),
-                None, dz.data_ptr(), Fr, C, P, stream), "rk_bn_bwd_dx_pre")                       # in place: dz -> d(z)
+            ws, nb = _native.workspace("rk2d_backward_bn_workspace_bytes", dev, Fr, C, H, W, sH, sW, pH, pW)
+            _native.call("rk2d_backward_bn_" + _BNReLUShift2DTrain._SHIFT_SFX[z.dtype], gy.data_ptr(), z.data_ptr(),
+                         abmi.data_ptr(), shift.data_ptr(), dz.data_ptr(), gshift.data_ptr(), k12.data_ptr(), dgamma.data_ptr(),
+                         dbeta.data_ptr(), Fr, C, H, W, sH, sW, pH, pW, int(ctx.normalize_grad), 0, ws.data_ptr(), nb, stream)
+            _native.call("rk_bn_bwd_dx_pre_" + sfx, dz.data_ptr(), z.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                         save_invstd.data_ptr(), k12.data_ptr(), None, dz.data_ptr(), Fr, C, P, stream)      # in place: dz -> d(z)
         return (dz, dgamma.to(weight.dtype), dbeta.to(bias.dtype), gshift) + (None,) * 9
 
 
@@ -452,21 +417,16 @@ def bn_relu_shift2d(bn, as3, z):
     momentum, counter = _count_batch(bn)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    return _BNReLUShift2DTrain.apply(z, bn.weight, bn.bias, shift, rm, rv, momentum, bn.eps, _ptr(counter),
+    return _BNReLUShift2DTrain.apply(z, bn.weight, bn.bias, shift, rm, rv, momentum, bn.eps, _native.ptr(counter),
                                      bool(getattr(as3, "normalize_grad", True)), take_stats(z), stride, padding)
 
 
 def _eval_forward(x, weight, bias, running_mean, running_var, eps, relu):
-    L = _native.lib()
     Fr, C, H, W = x.shape
-    dev = x.device
     y = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = getattr(L, "rk_bn_relu_forward_" + _SFX[x.dtype])(
-            x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
-            None, None, y.data_ptr(), Fr, C, H * W, float(eps), 0.0, int(relu), 0, None, 0,
-            torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, "rk_bn_relu_forward")
+    _native.launch("rk_bn_relu_forward_" + _SFX[x.dtype], x.device, x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                   running_mean.data_ptr(), running_var.data_ptr(), None, None, y.data_ptr(), Fr, C, H * W, float(eps), 0.0,
+                   int(relu), 0, None, 0)
     return y
 
 
@@ -508,7 +468,7 @@ def bn_relu_skip(bn, x):
         momentum, counter = _count_batch(bn)
         rm = bn.running_mean if (bn.training and bn.track_running_stats) else None
         rv = bn.running_var if (bn.training and bn.track_running_stats) else None
-        return _BNReLUTrain.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, True, True, _ptr(counter),
+        return _BNReLUTrain.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, True, True, _native.ptr(counter),
                                   take_stats(x) if bn.training else None)
     return bn_relu(bn, x), x
 
@@ -524,7 +484,7 @@ def bn_relu(bn, x, relu=True):
         momentum, counter = _count_batch(bn)
         rm = bn.running_mean if (bn.training and bn.track_running_stats) else None
         rv = bn.running_var if (bn.training and bn.track_running_stats) else None
-        return _BNReLUTrain.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, relu, False, _ptr(counter),
+        return _BNReLUTrain.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, relu, False, _native.ptr(counter),
                                   take_stats(x) if bn.training else None)
     if torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
         y = bn(x)                                  # frozen-statistics fine-tuning: stock kernels

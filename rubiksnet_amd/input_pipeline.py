@@ -58,11 +58,8 @@ def stacked_u8_to_clips(stacked, n_frames, mean=IMAGENET_MEAN, std=IMAGENET_STD,
         raise RuntimeError("out must be a contiguous %s tensor [B, 3T, H, W]" % dtype)
     ms = _mean_std_on(dev, mean, std)
     if B:
-        with torch.cuda.device(dev):
-            rc = getattr(_native.lib(), "rk_clip_u8_to_chw_" + _SFX[dtype])(
-                stacked.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr(), out.data_ptr(), B, H, W, CS,
-                torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_clip_u8_to_chw")
+        _native.launch("rk_clip_u8_to_chw_" + _SFX[dtype], dev, stacked.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr(),
+                       out.data_ptr(), B, H, W, CS)
     return out.view(B, n_frames, 3, H, W)
 
 

@@ -342,12 +342,9 @@ def launch_decode(streams, frames, qtabs, htabs, n, rgb, workspace, status, nq=N
     nh = htabs.numel() // HUFF_DTYPE.itemsize if nh is None else nh
     if qtabs.numel() < nq * 128 or htabs.numel() < nh * HUFF_DTYPE.itemsize:
         raise ValueError("the table arenas are shorter than nq / nh say")
-    with torch.cuda.device(rgb.device):
-        rc = _native.lib().rk_jpeg_decode_u8(
-            streams.data_ptr(), streams.numel(), frames.data_ptr(), qtabs.data_ptr(), htabs.data_ptr(), nq, nh, n,
-            rgb.data_ptr(), rgb.numel(), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
-            torch.cuda.current_stream(rgb.device).cuda_stream)
-    _native.check(rc, "rk_jpeg_decode_u8")
+    _native.launch("rk_jpeg_decode_u8", rgb.device, streams.data_ptr(), streams.numel(), frames.data_ptr(), qtabs.data_ptr(),
+                   htabs.data_ptr(), nq, nh, n, rgb.data_ptr(), rgb.numel(), workspace.data_ptr(), workspace.numel(),
+                   status.data_ptr())
 
 
 def sections(blob, layout):

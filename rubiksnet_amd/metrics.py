@@ -166,11 +166,8 @@ class StreamMeter:
             out["loss"] = torch.empty(B, dtype=torch.float32, device=dev)
         entry = "rk_metrics_update_" + _NATIVE[logits.dtype]
         ks = (self.topk + (1,) * MAX_TOPK)[:MAX_TOPK]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _native.check(getattr(self._lib, entry)(
-                logits.data_ptr(), labels.data_ptr(), state.data_ptr(), B, self.views, K, int(self.confusion),
-                len(self.topk), *ks, *(out[name].data_ptr() if name in out else None for name in OUTPUTS), stream), entry)
+        _native.launch(entry, dev, logits.data_ptr(), labels.data_ptr(), state.data_ptr(), B, self.views, K, int(self.confusion),
+                       len(self.topk), *ks, *(_native.ptr(out.get(name)) for name in OUTPUTS))
         return out
 
     def _update_torch(self, logits, labels, state, B):

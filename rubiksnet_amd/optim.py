@@ -77,7 +77,7 @@ def chunk_partition(numels):
     """(chunk size, chunks in all, first chunk of every tensor) as the kernels cut `numels` (rk_debug_optim_chunks)."""
     n = len(numels)
     out = (ctypes.c_int * (n + 2))()
-    _native.check(_native.lib().rk_debug_optim_chunks((ctypes.c_longlong * n)(*numels), n, out), "rk_debug_optim_chunks")
+    _native.call("rk_debug_optim_chunks", (ctypes.c_longlong * n)(*numels), n, out)
     return out[0], out[1], list(out[2:])
 
 

@@ -6,10 +6,9 @@ used as it is and d(weight) comes out in fp32 -- no casts; arithmetic is fp32 MF
 with H*W % 4 == 0 and even channel
 counts, d(weight) always runs on the HIP kernels (fp32: 2.6x / 2.3x / 2.0x / 1.25x MIOpen's at 56x56 / 54->108 /
 28x28 / 14x14; bf16, on the bf16 MFMA: 2.4x / 3.2x / 3.9x / 1.7x: MIOpen's NHWC implicit GEMM needs two layout
-transposes), and forward / d(input) do where they win -- the
-memory-bound 112x112 / 56x56 stages; elsewhere they stay on aten (MIOpen).  Other dtypes, 7x7 planes, strided
-shortcuts, CPU tensors: `conv(x)`.  `RK_PW=0` disables the HIP path, `RK_PW=all` forces the HIP GEMM wherever
-the kernel's constraints allow (config.py).  Forward, d(input) and d(weight) are HIP MFMA kernels.
+transposes), and so do forward / d(input) (measured on the train steps the HIP GEMM wins wherever it can run, `_eligible`).
+7x7 planes and the stride-2 projecting shortcuts have kernels of their own (`conv1x1` tries them first); other dtypes, odd
+channel counts, CPU tensors: `conv(x)`.  `RK_PW=0` disables the HIP path; `RK_PW=all` means the same as `auto` (config.py).
 """
 import contextlib
 import struct
@@ -76,10 +75,8 @@ def prepacked(module):
         plan = (key, jobs, off, max_units, views)
         module._rk_prepack_plan = plan                      # (rebuilt when a weight moves: .to(), a reloaded parameter)
     _, jobs, total, max_units, views = plan
-    with torch.cuda.device(dev):
-        buf = torch.empty(total, dtype=torch.uint8, device=dev)
-        _native.check(L.rk_pw_pack_many_bf16(jobs.data_ptr(), len(weights), buf.data_ptr(), max_units,
-                                             torch.cuda.current_stream(dev).cuda_stream), "rk_pw_pack_many_bf16")
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)
+    _native.launch("rk_pw_pack_many_bf16", dev, jobs.data_ptr(), len(weights), buf.data_ptr(), max_units)
     _TABLES.prepacked = {w.data_ptr(): (tuple(w.shape[:2]), buf[o:o + bf], buf[o + bf:o + bf + bb])
                          for w, (o, bf, bb) in zip(weights, views)}
     try:
@@ -101,11 +98,9 @@ def _pack(weight):
     L = _native.lib()
     Cout, Cin = weight.shape[0], weight.shape[1]
     dev = weight.device
-    with torch.cuda.device(dev):
-        fwd = torch.empty(int(L.rk_pw_packed_bytes(Cout, Cin)), dtype=torch.uint8, device=dev)
-        bwd = torch.empty(int(L.rk_pw_packed_bytes(Cin, Cout)), dtype=torch.uint8, device=dev)
-        _native.check(L.rk_pw_pack_bf16(weight.data_ptr(), Cout, Cin, fwd.data_ptr(), bwd.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream), "rk_pw_pack_bf16")
+    fwd = torch.empty(int(L.rk_pw_packed_bytes(Cout, Cin)), dtype=torch.uint8, device=dev)
+    bwd = torch.empty(int(L.rk_pw_packed_bytes(Cin, Cout)), dtype=torch.uint8, device=dev)
+    _native.launch("rk_pw_pack_bf16", dev, weight.data_ptr(), Cout, Cin, fwd.data_ptr(), bwd.data_ptr())
     return fwd, bwd
 
 
@@ -130,22 +125,12 @@ def _gemm(a, x, out, Fr, K, M, P, a_is_mk, residual=None, packed=None):
         # bf16 activations: the packed-weight kernel (`packed`: the operand, packed by the caller's forward)
         if packed is None:
             packed = _pack(a)[0 if a_is_mk else 1]
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_pw_gemm_packed_bf16(
-                packed.data_ptr(), x.data_ptr(), residual.data_ptr() if residual is not None else None,
-                out.data_ptr(), Fr, K, M, P, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_pw_gemm_packed_bf16")
+        _native.launch("rk_pw_gemm_packed_bf16", dev, packed.data_ptr(), x.data_ptr(), _native.ptr(residual), out.data_ptr(),
+                       Fr, K, M, P)
         return out
-    fn = getattr(_native.lib(), "rk_pw_gemm_" + _SFX[x.dtype])
-    with torch.cuda.device(dev):
-        rc = fn(a.data_ptr(), x.data_ptr(), residual.data_ptr() if residual is not None else None, out.data_ptr(),
-                Fr, K, M, P, int(a_is_mk), torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, "rk_pw_gemm")
+    _native.launch("rk_pw_gemm_" + _SFX[x.dtype], dev, a.data_ptr(), x.data_ptr(), _native.ptr(residual), out.data_ptr(),
+                   Fr, K, M, P, int(a_is_mk))
     return out
-
-
-def _as(weight, dtype):
-    return weight if weight.dtype == dtype else weight.to(dtype)
 
 
 def _wgrad(dy, x, weight):
@@ -154,63 +139,42 @@ def _wgrad(dy, x, weight):
     Fr, Cin, H, W = x.shape
     Cout = weight.shape[0]
     dev = x.device
-    L = _native.lib()
     dw = torch.empty_like(weight)                       # fp32, whatever the activations' storage type
-    with torch.cuda.device(dev):
-        if x.dtype == torch.bfloat16 and H * W >= 8 and _pw16_fits(Fr, max(Cin, Cout), H * W):
-            nbytes = int(L.rk_pw_wgrad16_workspace_bytes(Fr, Cin, Cout, H * W))
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            _native.check(L.rk_pw_wgrad16_bf16(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W, ws.data_ptr(),
-                                               nbytes, torch.cuda.current_stream(dev).cuda_stream), "rk_pw_wgrad16_bf16")
-            return dw
-        nbytes = int(L.rk_pw_wgrad_workspace_bytes(Fr, Cin, Cout, H * W))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        rc = getattr(L, "rk_pw_wgrad_" + _SFX[x.dtype])(
-            dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W, ws.data_ptr(), nbytes,
-            torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, "rk_pw_wgrad")
+    if x.dtype == torch.bfloat16 and H * W >= 8 and _pw16_fits(Fr, max(Cin, Cout), H * W):
+        query, name = "rk_pw_wgrad16_workspace_bytes", "rk_pw_wgrad16_bf16"
+    else:
+        query, name = "rk_pw_wgrad_workspace_bytes", "rk_pw_wgrad_" + _SFX[x.dtype]
+    ws, nbytes = _native.workspace(query, dev, Fr, Cin, Cout, H * W)
+    _native.launch(name, dev, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W, ws.data_ptr(), nbytes)
     return dw
 
 
-_ATEN_ARGS = ([1, 1], [0, 0], [1, 1], False, [0, 0], 1)
-
-
 class _Conv1x1Func(torch.autograd.Function):
-    """1x1 convolution; `hip_gemm` selects the HIP GEMM for forward / d(input) (else aten = MIOpen);
-    d(weight) is the HIP kernel either way (it wins on every shape: MIOpen's needs two layout transposes)."""
+    """1x1 convolution (+ residual) on the HIP GEMM: forward, d(input) and d(weight) (MIOpen's d(weight) needs two layout
+    transposes: the HIP kernel wins on every shape)."""
 
     @staticmethod
-    def forward(ctx, x, weight, hip_gemm, residual, hip_dx=None, want_stats=False):
+    def forward(ctx, x, weight, residual, want_stats=False):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         ctx.packed_bwd = None
         stats = None
-        if hip_gemm:
-            y = torch.empty(Fr, Cout, H, W, dtype=x.dtype, device=x.device)
-            fwd = None
-            if _packed_ok(weight, x, Cin, Cout, H * W, True):
-                fwd, ctx.packed_bwd = _pack(weight)
-            if want_stats and fwd is not None and residual is None:
-                # (conv2 -> bn2 only: with the residual's 72 registers on top of 144 accumulators the statistics variant of
-                # the 288-row kernel spills, and the 144-row one drops from 3 to 2 waves per SIMD: measured slower than the
-                # statistics pass it saves)
-                # training: the GEMM also leaves the tile statistics of y for the BatchNorm that consumes it (fused_bn.py)
-                L = _native.lib()
-                J = int(L.rk_pw16_stat_tiles(Fr, H * W))
-                stats = torch.empty(Cout, J, 4, dtype=torch.float32, device=x.device)
-                with torch.cuda.device(x.device):
-                    _native.check(L.rk_pw_gemm_packed_stats_bf16(
-                        fwd.data_ptr(), x.data_ptr(), residual.data_ptr() if residual is not None else None, y.data_ptr(), Fr, Cin,
-                        Cout, H * W, stats.data_ptr(), J, torch.cuda.current_stream(x.device).cuda_stream),
-                        "rk_pw_gemm_packed_stats_bf16")
-            else:
-                _gemm(weight, x, y, Fr, Cin, Cout, H * W, True, residual, fwd)  # `+ residual` in the GEMM's epilogue
+        y = torch.empty(Fr, Cout, H, W, dtype=x.dtype, device=x.device)
+        fwd = None
+        if _packed_ok(weight, x, Cin, Cout, H * W, True):
+            fwd, ctx.packed_bwd = _pack(weight)
+        if want_stats and fwd is not None and residual is None:
+            # (conv2 -> bn2 only: with the residual's 72 registers on top of 144 accumulators the statistics variant of
+            # the 288-row kernel spills, and the 144-row one drops from 3 to 2 waves per SIMD: measured slower than the
+            # statistics pass it saves)
+            # training: the GEMM also leaves the tile statistics of y for the BatchNorm that consumes it (fused_bn.py)
+            J = int(_native.lib().rk_pw16_stat_tiles(Fr, H * W))
+            stats = torch.empty(Cout, J, 4, dtype=torch.float32, device=x.device)
+            _native.launch("rk_pw_gemm_packed_stats_bf16", x.device, fwd.data_ptr(), x.data_ptr(), None, y.data_ptr(), Fr, Cin,
+                           Cout, H * W, stats.data_ptr(), J)
         else:
-            y = torch.ops.aten.convolution(x, _as(weight, x.dtype), None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1)
-            if residual is not None:
-                y.add_(residual)
+            _gemm(weight, x, y, Fr, Cin, Cout, H * W, True, residual, fwd)  # `+ residual` in the GEMM's epilogue
         ctx.save_for_backward(x, weight)
-        ctx.hip_dx = hip_gemm if hip_dx is None else hip_dx
         ctx.has_residual = residual is not None
         if want_stats:
             if stats is None:
@@ -224,63 +188,60 @@ class _Conv1x1Func(torch.autograd.Function):
     def backward(ctx, dy, _dstats=None):
         x, weight = ctx.saved_tensors
         if dy is None:
-            return (None,) * 6
+            return (None,) * 4
         dy = dy.contiguous()
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            if ctx.hip_dx:
-                Fr, Cin, H, W = x.shape
-                dx = torch.empty_like(x)
-                _gemm(weight, dy, dx, Fr, weight.shape[0], Cin, H * W, False, None, ctx.packed_bwd)     # W read as [K=Cout][M=Cin]
-            else:
-                dx = torch.ops.aten.convolution_backward(dy, x, _as(weight, x.dtype), None, *_ATEN_ARGS,
-                                                         [True, False, False])[0]
+            Fr, Cin, H, W = x.shape
+            dx = torch.empty_like(x)
+            _gemm(weight, dy, dx, Fr, weight.shape[0], Cin, H * W, False, None, ctx.packed_bwd)     # W read as [K=Cout][M=Cin]
         if ctx.needs_input_grad[1]:
             dw = _wgrad(dy, x, weight)
-        return dx, dw, None, (dy if ctx.has_residual and ctx.needs_input_grad[3] else None), None, None
+        return dx, dw, (dy if ctx.has_residual and ctx.needs_input_grad[2] else None), None
 
 
-def _eligible(conv, x, has_residual=False):
-    """None: stock path; else whether forward / d(input) should use the HIP GEMM too."""
-    mode = pointwise_mode()
-    if mode == "0" or not (x.is_cuda and x.dtype in _SFX and x.dim() == 4):
-        return None
+def _is_1x1(conv, stride):
+    """A bias-free 1x1 nn.Conv2d with an fp32 weight and stride (stride, stride): what every HIP route asks of the layer."""
+    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (stride, stride)
+            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32)
+
+
+def _eligible(conv, x):
+    """Whether the stride-1 HIP GEMMs run this layer (else: the stock path)."""
+    if pointwise_mode() == "0" or not (x.is_cuda and x.dtype in _SFX and x.dim() == 4):
+        return False
     if x.dtype == torch.float32 and torch.is_autocast_enabled():
-        return None                                       # autocast would run this layer in bf16: let it
-    if not (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None
-            and conv.weight.dtype == torch.float32):
-        return None
+        return False                                      # autocast would run this layer in bf16: let it
+    if not _is_1x1(conv, 1):
+        return False
     P = x.shape[2] * x.shape[3]
     K, M = conv.in_channels, conv.out_channels
-    if P % 4 or K % 2 or M % 2 or x.numel() == 0:      # kernel constraints (M even: it is K of the d(input) GEMM)
-        return None
+    # kernel constraints (M even: it is K of the d(input) GEMM)
     # Round 1 restricted "auto" to a per-plane-size channel window measured with isolated, event-bracketed probes
     # (tools/pointwise_probe.py).  Measured on the train steps themselves the HIP GEMM wins wherever it can run
     # (RK_PW=all against that window: Large-AQ bf16 49.3 -> 45.0 ms, Large 74.4 -> 73.5, Small 44.9 -> 44.3,
-    # Tiny 25.8 -> 25.6, Tiny forward b64 equal), so "auto" and "all" now mean the same.
-    return True
+    # Tiny 25.8 -> 25.6, Tiny forward b64 equal), so "auto" and "all" mean the same: no narrower window here.
+    return not (P % 4 or K % 2 or M % 2 or x.numel() == 0)
 
 
 class _ConvS2Func(torch.autograd.Function):
     """1x1 / stride-2 convolution (the projecting shortcut of a downsampling block) on the HIP GEMM kernels:
     forward reads the activation at stride 2, d(input) scatters into the even positions (zeros elsewhere, every
     element written), d(weight) gathers like the forward.  MIOpen runs these as two asm kernels + an implicit-GEMM
-    d(weight) between layout transposes (1.3 ms + of a Tiny train step)."""
+    d(weight) between layout transposes (1.3 ms + of a Tiny train step).  `odd`: "" (Ho * Wo % 4 == 0) or "_odd", the
+    kernels for output planes with Ho * Wo % 4 != 0 (14x14 -> 7x7)."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, odd):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         y = torch.empty(Fr, Cout, H // 2, W // 2, dtype=x.dtype, device=x.device)
-        dev = x.device
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_pw_s2_forward_f32(weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W,
-                                                    torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_pw_s2_forward_f32")
+        _native.launch("rk_pw_s2_forward%s_f32" % odd, x.device, weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout,
+                       H, W)
         ctx.save_for_backward(x, weight)
+        ctx.odd = odd
         return y
 
     @staticmethod
@@ -289,75 +250,58 @@ class _ConvS2Func(torch.autograd.Function):
         dy = dy.contiguous()
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
-        dev = x.device
-        L = _native.lib()
+        dev, odd = x.device, ctx.odd
         dx = dw = None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _native.check(L.rk_pw_s2_dgrad_f32(weight.data_ptr(), dy.data_ptr(), dx.data_ptr(), Fr, Cin, Cout, H, W,
-                                                   stream), "rk_pw_s2_dgrad_f32")
-            if ctx.needs_input_grad[1]:
-                dw = torch.empty_like(weight)
-                nbytes = int(L.rk_pw_wgrad_workspace_bytes(Fr, Cin, Cout, (H // 2) * (W // 2)))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                _native.check(L.rk_pw_s2_wgrad_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H, W,
-                                                   ws.data_ptr(), nbytes, stream), "rk_pw_s2_wgrad_f32")
-        return dx, dw
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _native.launch("rk_pw_s2_dgrad%s_f32" % odd, dev, weight.data_ptr(), dy.data_ptr(), dx.data_ptr(), Fr, Cin, Cout,
+                           H, W)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weight)
+            ws, nbytes = _native.workspace("rk_pw_wgrad%s_workspace_bytes" % odd, dev, Fr, Cin, Cout, (H // 2) * (W // 2))
+            _native.launch("rk_pw_s2_wgrad%s_f32" % odd, dev, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H, W,
+                           ws.data_ptr(), nbytes)
+        return dx, dw, None
+
+
+class _ConvS2OddFunc(_ConvS2Func):
+    """_ConvS2Func under the name its "_odd" route shows in the autograd graph (14x14 -> 7x7); no code of its own."""
 
 
 def _eligible_s2(conv, x):
     return (pointwise_mode() != "0" and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
-            and not torch.is_autocast_enabled()
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (2, 2)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
+            and not torch.is_autocast_enabled() and _is_1x1(conv, 2)
             and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
             and max(conv.in_channels, conv.out_channels) <= _S2_CMAX
             and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and ((x.shape[2] // 2) * (x.shape[3] // 2)) % 4 == 0)
 
 
-class _ConvS2Bf16Func(torch.autograd.Function):
-    """The same projecting shortcut for bf16 activations (autocast): the even pixels are gathered once (a strided copy: a
-    quarter of the elements), and the three GEMMs run on the stride-1 bf16 kernels of rk_pw16.hip on that quarter-size
-    tensor -- which is also what is saved for backward.  d(input) is scattered back into zeros.  MIOpen ran these between
-    NCHW <-> NHWC transposes of the FULL-size tensors: 0.5 / 0.8 ms forward / backward at [256, 72, 112, 112]."""
+class _GatherS2(torch.autograd.Function):
+    """x -> x[:, :, ::2, ::2] gathered (a strided copy: a quarter of the elements): what a stride-2 projecting shortcut reads
+    of bf16 activations (autocast).  The stride-1 bf16 kernels then run on that quarter-size tensor -- which is also what
+    they save for backward -- and d(input) is scattered back into zeros here.  MIOpen ran these shortcuts between NCHW <->
+    NHWC transposes of the FULL-size tensors: 0.5 / 0.8 ms forward / backward at [256, 72, 112, 112]."""
 
     @staticmethod
-    def forward(ctx, x, weight):
-        Fr, Cin, H, W = x.shape
-        Cout = weight.shape[0]
-        xs = x[:, :, ::2, ::2].contiguous()
-        y = torch.empty(Fr, Cout, H // 2, W // 2, dtype=x.dtype, device=x.device)
-        fwd, ctx.packed_bwd = _pack(weight)
-        _gemm(weight, xs, y, Fr, Cin, Cout, (H // 2) * (W // 2), True, None, fwd)
-        ctx.save_for_backward(xs, weight)
-        ctx.full = (H, W)
-        return y
+    def forward(ctx, x):
+        ctx.shape = tuple(x.shape)
+        return x[:, :, ::2, ::2].contiguous()
 
     @staticmethod
-    def backward(ctx, dy):
-        xs, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != xs.dtype:
-            dy = dy.to(xs.dtype)
-        Fr, Cin, Ho, Wo = xs.shape
-        H, W = ctx.full
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dxs = torch.empty_like(xs)
-            _gemm(weight, dy, dxs, Fr, weight.shape[0], Cin, Ho * Wo, False, None, ctx.packed_bwd)
-            dx = torch.zeros(Fr, Cin, H, W, dtype=xs.dtype, device=xs.device)
-            dx[:, :, ::2, ::2] = dxs
-        if ctx.needs_input_grad[1]:
-            dw = _wgrad(dy, xs, weight)
-        return dx, dw
+    def backward(ctx, dxs):
+        dx = torch.zeros(ctx.shape, dtype=dxs.dtype, device=dxs.device)
+        dx[:, :, ::2, ::2] = dxs
+        return dx
+
+
+class _ConvS2Bf16Func(_Conv1x1Func):
+    """_Conv1x1Func under the name the bf16 stride-2 route (on the operand of _GatherS2) shows in the autograd graph; no code
+    of its own."""
 
 
 def _eligible_s2_bf16(conv, x):
     return (pointwise_mode() != "0" and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.numel() > 0
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (2, 2)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
+            and _is_1x1(conv, 2)
             and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
             and ((x.shape[2] // 2) * (x.shape[3] // 2)) % 4 == 0 and (x.shape[2] // 2) * (x.shape[3] // 2) >= 8
             and _pw16_fits(x.shape[0], max(conv.in_channels, conv.out_channels), (x.shape[2] // 2) * (x.shape[3] // 2)))
@@ -373,12 +317,8 @@ class _Conv1x1OddFunc(torch.autograd.Function):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         y = torch.empty(Fr, Cout, H, W, dtype=x.dtype, device=x.device)
-        dev = x.device
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_pw_gemm_odd_f32(weight.data_ptr(), x.data_ptr(),
-                                                  residual.data_ptr() if residual is not None else None, y.data_ptr(),
-                                                  Fr, Cin, Cout, H * W, 1, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_pw_gemm_odd_f32")
+        _native.launch("rk_pw_gemm_odd_f32", x.device, weight.data_ptr(), x.data_ptr(), _native.ptr(residual), y.data_ptr(),
+                       Fr, Cin, Cout, H * W, 1)
         ctx.save_for_backward(x, weight)
         ctx.has_residual = residual is not None
         return y
@@ -390,87 +330,33 @@ class _Conv1x1OddFunc(torch.autograd.Function):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         dev = x.device
-        L = _native.lib()
         dx = dw = None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _native.check(L.rk_pw_gemm_odd_f32(weight.data_ptr(), dy.data_ptr(), None, dx.data_ptr(), Fr, Cout, Cin,
-                                                   H * W, 0, stream), "rk_pw_gemm_odd_f32")
-            if ctx.needs_input_grad[1]:
-                dw = torch.empty_like(weight)
-                nbytes = int(L.rk_pw_wgrad_odd_workspace_bytes(Fr, Cin, Cout, H * W))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                _native.check(L.rk_pw_wgrad_odd_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W,
-                                                    ws.data_ptr(), nbytes, stream), "rk_pw_wgrad_odd_f32")
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _native.launch("rk_pw_gemm_odd_f32", dev, weight.data_ptr(), dy.data_ptr(), None, dx.data_ptr(), Fr, Cout, Cin,
+                           H * W, 0)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weight)
+            ws, nbytes = _native.workspace("rk_pw_wgrad_odd_workspace_bytes", dev, Fr, Cin, Cout, H * W)
+            _native.launch("rk_pw_wgrad_odd_f32", dev, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W,
+                           ws.data_ptr(), nbytes)
         return dx, dw, (dy if ctx.has_residual and ctx.needs_input_grad[2] else None)
-
-
-class _ConvS2OddFunc(torch.autograd.Function):
-    """The 1x1 / stride-2 projecting shortcut onto planes with Ho * Wo % 4 != 0 (14x14 -> 7x7)."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        Fr, Cin, H, W = x.shape
-        Cout = weight.shape[0]
-        y = torch.empty(Fr, Cout, H // 2, W // 2, dtype=x.dtype, device=x.device)
-        dev = x.device
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_pw_s2_forward_odd_f32(weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W,
-                                                        torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_pw_s2_forward_odd_f32")
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        Fr, Cin, H, W = x.shape
-        Cout = weight.shape[0]
-        dev = x.device
-        L = _native.lib()
-        dx = dw = None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _native.check(L.rk_pw_s2_dgrad_odd_f32(weight.data_ptr(), dy.data_ptr(), dx.data_ptr(), Fr, Cin, Cout, H, W,
-                                                       stream), "rk_pw_s2_dgrad_odd_f32")
-            if ctx.needs_input_grad[1]:
-                dw = torch.empty_like(weight)
-                nbytes = int(L.rk_pw_wgrad_odd_workspace_bytes(Fr, Cin, Cout, (H // 2) * (W // 2)))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                _native.check(L.rk_pw_s2_wgrad_odd_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H, W,
-                                                       ws.data_ptr(), nbytes, stream), "rk_pw_s2_wgrad_odd_f32")
-        return dx, dw
 
 
 class _Conv1x1Odd16Func(torch.autograd.Function):
     """1x1 convolution (+ residual) of bf16 activations on planes with H * W % 4 != 0 (the 7x7 planes of layer4 under
-    autocast; `stride` 2: the 14x14 -> 7x7 projecting shortcut, its even pixels gathered first as in _ConvS2Bf16Func) on
+    autocast; also the 14x14 -> 7x7 projecting shortcut, on its even pixels gathered by _GatherS2) on
     rk_pw16_odd.hip: a workgroup per frame, the packed weight of rk_pw_pack_bf16.  MIOpen ran these as NHWC implicit GEMMs
     between two layout transposes of each tensor: 58 / 173 us forward / forward + backward at [256, 576 -> 576, 7, 7]."""
 
     @staticmethod
-    def forward(ctx, x, weight, residual, stride):
-        if stride == 2:
-            H, W = x.shape[2], x.shape[3]
-            ctx.full = (H, W)
-            x = x[:, :, ::2, ::2].contiguous()
-        else:
-            ctx.full = None
+    def forward(ctx, x, weight, residual):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         y = torch.empty(Fr, Cout, H, W, dtype=x.dtype, device=x.device)
         fwd, ctx.packed_bwd = _pack(weight)
-        dev = x.device
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_pw_gemm_packed_odd_bf16(fwd.data_ptr(), x.data_ptr(),
-                                                          residual.data_ptr() if residual is not None else None, y.data_ptr(),
-                                                          Fr, Cin, Cout, H * W, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_pw_gemm_packed_odd_bf16")
+        _native.launch("rk_pw_gemm_packed_odd_bf16", x.device, fwd.data_ptr(), x.data_ptr(), _native.ptr(residual),
+                       y.data_ptr(), Fr, Cin, Cout, H * W)
         ctx.save_for_backward(x, weight)
         ctx.has_residual = residual is not None
         return y
@@ -484,33 +370,22 @@ class _Conv1x1Odd16Func(torch.autograd.Function):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         dev = x.device
-        L = _native.lib()
         dx = dw = None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _native.check(L.rk_pw_gemm_packed_odd_bf16(ctx.packed_bwd.data_ptr(), dy.data_ptr(), None, dx.data_ptr(), Fr, Cout,
-                                                           Cin, H * W, stream), "rk_pw_gemm_packed_odd_bf16")
-                if ctx.full is not None:
-                    full = torch.zeros(Fr, Cin, ctx.full[0], ctx.full[1], dtype=x.dtype, device=dev)
-                    full[:, :, ::2, ::2] = dx
-                    dx = full
-            if ctx.needs_input_grad[1]:
-                dw = torch.empty_like(weight)
-                nbytes = int(L.rk_pw_wgrad_odd16_workspace_bytes(Fr, Cin, Cout, H * W))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                _native.check(L.rk_pw_wgrad_odd16_bf16(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W,
-                                                       ws.data_ptr(), nbytes, stream), "rk_pw_wgrad_odd16_bf16")
-        return dx, dw, (dy if ctx.has_residual and ctx.needs_input_grad[2] else None), None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _native.launch("rk_pw_gemm_packed_odd_bf16", dev, ctx.packed_bwd.data_ptr(), dy.data_ptr(), None, dx.data_ptr(),
+                           Fr, Cout, Cin, H * W)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weight)
+            ws, nbytes = _native.workspace("rk_pw_wgrad_odd16_workspace_bytes", dev, Fr, Cin, Cout, H * W)
+            _native.launch("rk_pw_wgrad_odd16_bf16", dev, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), Fr, Cin, Cout, H * W,
+                           ws.data_ptr(), nbytes)
+        return dx, dw, (dy if ctx.has_residual and ctx.needs_input_grad[2] else None)
 
 
 def _eligible_odd16(conv, x, stride):
     if not (pointwise_mode() != "0" and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.numel() > 0
-            and x.data_ptr() % 16 == 0
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (stride, stride)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.weight.is_cuda):
+            and x.data_ptr() % 16 == 0 and _is_1x1(conv, stride) and conv.weight.is_cuda):
         return False
     H, W = x.shape[2], x.shape[3]
     if stride == 2:
@@ -546,20 +421,14 @@ class _ForkS2(torch.autograd.Function):
             if g_main.dtype != g_small.dtype:
                 g_main = g_main.to(g_small.dtype)
         out = torch.empty(ctx.shape, dtype=g_small.dtype, device=g_small.device)
-        dev = g_small.device
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_scatter2x2_add_bf16(g_main.data_ptr() if g_main is not None else None, g_small.data_ptr(),
-                                                      out.data_ptr(), Fr * C, H, W, torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_scatter2x2_add_bf16")
+        _native.launch("rk_scatter2x2_add_bf16", g_small.device, _native.ptr(g_main), g_small.data_ptr(), out.data_ptr(),
+                       Fr * C, H, W)
         return out
 
 
 def _gathered_kind(conv, Fr, P, dtype, device_ok=True):
     """Which HIP kernels run the stride-2 projecting shortcut `conv` on its GATHERED operand [Fr, K, P]: "pw16" / "odd16" / None."""
-    if not (pointwise_mode() != "0" and dtype == torch.bfloat16
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (2, 2)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.weight.is_cuda):
+    if not (pointwise_mode() != "0" and dtype == torch.bfloat16 and _is_1x1(conv, 2) and conv.weight.is_cuda):
         return None
     K, M = conv.in_channels, conv.out_channels
     L = _native.lib()
@@ -573,8 +442,8 @@ def _gathered_kind(conv, Fr, P, dtype, device_ok=True):
 def conv_on_gathered(conv, xs, kind):
     """The stride-2 shortcut `conv` applied to its already gathered operand xs = x[:, :, ::2, ::2] (kind: _gathered_kind)."""
     if kind == "pw16":
-        return _Conv1x1Func.apply(xs, conv.weight, True, None, True)
-    return _Conv1x1Odd16Func.apply(xs, conv.weight, None, 1)
+        return _Conv1x1Func.apply(xs, conv.weight, None)
+    return _Conv1x1Odd16Func.apply(xs, conv.weight, None)
 
 
 def fork_shortcut(conv, x):
@@ -596,9 +465,7 @@ _ODD_PMIN, _ODD_PMAX = 37, 64        # k_pw_gemm_odd: frames per 256-column tile
 
 def _odd_common(conv, x, stride):
     return (pointwise_mode() != "0" and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
-            and not torch.is_autocast_enabled() and x.data_ptr() % 16 == 0
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (stride, stride)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
+            and not torch.is_autocast_enabled() and x.data_ptr() % 16 == 0 and _is_1x1(conv, stride)
             and conv.in_channels % 4 == 0 and conv.out_channels % 4 == 0)
 
 
@@ -621,33 +488,31 @@ def conv1x1(conv, x, residual=None):
             x = m(x)
         conv = conv[-1]
     if residual is None and _eligible_s2(conv, x):
-        return _ConvS2Func.apply(x.contiguous(), conv.weight)
+        return _ConvS2Func.apply(x.contiguous(), conv.weight, "")
     if residual is None and _eligible_s2_bf16(conv, x):
-        return _ConvS2Bf16Func.apply(x, conv.weight)
+        return _ConvS2Bf16Func.apply(_GatherS2.apply(x), conv.weight, None)
     if x.dim() == 4 and x.is_contiguous() and x.dtype == torch.bfloat16:
         if residual is None and _eligible_odd16(conv, x, 2):
-            return _Conv1x1Odd16Func.apply(x, conv.weight, None, 2)
+            return _Conv1x1Odd16Func.apply(_GatherS2.apply(x), conv.weight, None)
         if (_eligible_odd16(conv, x, 1) and (residual is None or (residual.is_contiguous() and residual.dtype == x.dtype
                                                                      and residual.data_ptr() % 16 == 0))):
-            return _Conv1x1Odd16Func.apply(x, conv.weight, residual, 1)
+            return _Conv1x1Odd16Func.apply(x, conv.weight, residual)
     if x.dim() == 4 and x.is_contiguous():
         if residual is None and _eligible_s2_odd(conv, x):
-            return _ConvS2OddFunc.apply(x, conv.weight)
+            return _ConvS2OddFunc.apply(x, conv.weight, "_odd")
         if (_eligible_odd(conv, x) and (residual is None or (residual.is_contiguous() and residual.dtype == x.dtype))):
             return _Conv1x1OddFunc.apply(x, conv.weight, residual)
-    hip_gemm = _eligible(conv, x, residual is not None)
-    if hip_gemm is None or (residual is not None and not (residual.is_contiguous() and residual.dtype == x.dtype)):
+    if not _eligible(conv, x) or (residual is not None and not (residual.is_contiguous() and residual.dtype == x.dtype)):
         y = conv(x)
         if residual is not None:
             y += residual
         return y
-    hip_dx = hip_gemm
-    if (hip_gemm and x.dtype == torch.bfloat16 and conv.training and torch.is_grad_enabled() and config.switches().fused_train
+    if (x.dtype == torch.bfloat16 and conv.training and torch.is_grad_enabled() and config.switches().fused_train
             and config.switches().fused_bn and config.switches().pw16_stats):
         from .fused_bn import attach_stats
-        y, stats = _Conv1x1Func.apply(x.contiguous(), conv.weight, hip_gemm, residual, hip_dx, True)
+        y, stats = _Conv1x1Func.apply(x.contiguous(), conv.weight, residual, True)
         return attach_stats(y, stats) if stats.dim() == 3 else y
-    return _Conv1x1Func.apply(x.contiguous(), conv.weight, hip_gemm, residual, hip_dx)
+    return _Conv1x1Func.apply(x.contiguous(), conv.weight, residual)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -687,9 +552,7 @@ def prefolded(module):
         module._rk_prefold_plan = plan
     _, jobs, offs, total, max_c = plan
     ab = torch.empty(2, total, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _native.check(_native.lib().rk_bn_fold_many_f32(jobs.data_ptr(), len(bns), ab.data_ptr(), total, max_c,
-                                                        torch.cuda.current_stream(dev).cuda_stream), "rk_bn_fold_many_f32")
+    _native.launch("rk_bn_fold_many_f32", dev, jobs.data_ptr(), len(bns), ab.data_ptr(), total, max_c)
     _TABLES.prefolded = {id(m): (ab[0, o:o + int(m.weight.shape[0])], ab[1, o:o + int(m.weight.shape[0])]) for m, o in zip(bns, offs)}
     try:
         yield
@@ -710,11 +573,8 @@ def _bn_affine(bn):
     if all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (w, bias, mean, var)):
         ab = torch.empty(2, w.shape[0], dtype=torch.float32, device=w.device)
         a, b = ab[0], ab[1]
-        with torch.cuda.device(w.device):
-            rc = _native.lib().rk_bn_fold_f32(w.data_ptr(), bias.data_ptr(), mean.data_ptr(), var.data_ptr(), float(bn.eps),
-                                              a.data_ptr(), b.data_ptr(), w.shape[0],
-                                              torch.cuda.current_stream(w.device).cuda_stream)
-        _native.check(rc, "rk_bn_fold_f32")
+        _native.launch("rk_bn_fold_f32", w.device, w.data_ptr(), bias.data_ptr(), mean.data_ptr(), var.data_ptr(), float(bn.eps),
+                       a.data_ptr(), b.data_ptr(), w.shape[0])
         return a, b
     with torch.no_grad():
         a = (w.float() * torch.rsqrt(var.float() + bn.eps)).contiguous()
@@ -726,22 +586,16 @@ def _gemm_fused(conv, x, pro=None, epi=None, residual=None):
     Fr, Cin, H, W = x.shape
     Cout = conv.out_channels
     y = torch.empty(Fr, Cout, H, W, dtype=x.dtype, device=x.device)
-    dev = x.device
     ka, kb = pro if pro is not None else (None, None)
     ma, mb = epi if epi is not None else (None, None)
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-    with torch.cuda.device(dev):
-        rc = _native.lib().rk_pw_gemm_fused_f32(
-            conv.weight.data_ptr(), x.data_ptr(), ptr(residual), y.data_ptr(), Fr, Cin, Cout, H * W, 1,
-            ptr(ka), ptr(kb), 1, ptr(ma), ptr(mb), 1, torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, "rk_pw_gemm_fused_f32")
+    ptr = _native.ptr
+    _native.launch("rk_pw_gemm_fused_f32", x.device, conv.weight.data_ptr(), x.data_ptr(), ptr(residual), y.data_ptr(),
+                   Fr, Cin, Cout, H * W, 1, ptr(ka), ptr(kb), 1, ptr(ma), ptr(mb), 1)
     return y
 
 
 def _plain_1x1(conv, x):
-    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
+    return (_is_1x1(conv, 1) and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
             and max(conv.in_channels, conv.out_channels) <= _FUSED_EVAL_CMAX)
 
 
@@ -751,9 +605,7 @@ def _eval_bn(bn):
 
 
 def _strided_shortcut_ok(conv, x):
-    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (2, 2)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
+    return (_is_1x1(conv, 2) and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
             and max(conv.in_channels, conv.out_channels) <= _S2_CMAX and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
             and ((x.shape[2] // 2) * (x.shape[3] // 2)) % 4 == 0)
 
@@ -783,13 +635,9 @@ def _gemm_s2_fused(conv, x, pro):
     Fr, Cin, H, W = x.shape
     Cout = conv.out_channels
     y = torch.empty(Fr, Cout, H // 2, W // 2, dtype=x.dtype, device=x.device)
-    dev = x.device
     ka, kb = pro
-    with torch.cuda.device(dev):
-        rc = _native.lib().rk_pw_s2_forward_fused_f32(conv.weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W,
-                                                      ka.data_ptr(), kb.data_ptr(), 1,
-                                                      torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, "rk_pw_s2_forward_fused_f32")
+    _native.launch("rk_pw_s2_forward_fused_f32", x.device, conv.weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout,
+                   H, W, ka.data_ptr(), kb.data_ptr(), 1)
     return y
 
 
@@ -883,19 +731,15 @@ class _StemFunc(torch.autograd.Function):
         Cout = weight.shape[0]
         y = torch.empty(Fr, Cout, H // 2, W // 2, dtype=x.dtype, device=x.device)
         dev = x.device
-        L = _native.lib()
         stats = None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if with_stats:
-                # training: the statistics pass of the first block's bn1 rides on this GEMM's epilogue (train_block.py)
-                J = int(L.rk_pw_tiles(Fr, (H // 2) * (W // 2)))
-                stats = torch.empty(Cout, J, 4, dtype=torch.float32, device=dev)
-                rc = L.rk_stem_conv3x3s2_stats_f32(weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W,
-                                                   stats.data_ptr(), J, stream)
-            else:
-                rc = L.rk_stem_conv3x3s2_f32(weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W, stream)
-        _native.check(rc, "rk_stem_conv3x3s2_f32")
+        if with_stats:
+            # training: the statistics pass of the first block's bn1 rides on this GEMM's epilogue (train_block.py)
+            J = int(_native.lib().rk_pw_tiles(Fr, (H // 2) * (W // 2)))
+            stats = torch.empty(Cout, J, 4, dtype=torch.float32, device=dev)
+            _native.launch("rk_stem_conv3x3s2_stats_f32", dev, weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W,
+                           stats.data_ptr(), J)
+        else:
+            _native.launch("rk_stem_conv3x3s2_f32", dev, weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W)
         ctx.save_for_backward(x, weight)
         if with_stats:
             ctx.mark_non_differentiable(stats)
@@ -919,14 +763,10 @@ class _StemFunc(torch.autograd.Function):
             Fr, Cin, H, W = x.shape
             Cout = weight.shape[0]
             dev = x.device
-            L = _native.lib()
             gw = torch.empty_like(weight)
-            with torch.cuda.device(dev):
-                nbytes = int(L.rk_pw_wgrad_workspace_bytes(Fr, 9 * Cin, Cout, (H // 2) * (W // 2)))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                rc = L.rk_stem_wgrad3x3s2_f32(dy.data_ptr(), x.data_ptr(), gw.data_ptr(), Fr, Cin, Cout, H, W,
-                                              ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(rc, "rk_stem_wgrad3x3s2_f32")
+            ws, nbytes = _native.workspace("rk_pw_wgrad_workspace_bytes", dev, Fr, 9 * Cin, Cout, (H // 2) * (W // 2))
+            _native.launch("rk_stem_wgrad3x3s2_f32", dev, dy.data_ptr(), x.data_ptr(), gw.data_ptr(), Fr, Cin, Cout, H, W,
+                           ws.data_ptr(), nbytes)
         return gx, gw, None
 
 
@@ -939,11 +779,7 @@ class _Stem16Func(torch.autograd.Function):
         Fr, Cin, H, W = x.shape
         Cout = weight.shape[0]
         y = torch.empty(Fr, Cout, H // 2, W // 2, dtype=torch.bfloat16, device=x.device)
-        dev = x.device
-        with torch.cuda.device(dev):
-            rc = _native.lib().rk_stem_conv3x3s2_bf16out(weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W,
-                                                         torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(rc, "rk_stem_conv3x3s2_bf16out")
+        _native.launch("rk_stem_conv3x3s2_bf16out", x.device, weight.data_ptr(), x.data_ptr(), y.data_ptr(), Fr, Cin, Cout, H, W)
         ctx.save_for_backward(x, weight)
         return y
 
@@ -961,14 +797,10 @@ class _Stem16Func(torch.autograd.Function):
             Fr, Cin, H, W = x.shape
             Cout = weight.shape[0]
             dev = x.device
-            L = _native.lib()
             gw = torch.empty_like(weight)
-            with torch.cuda.device(dev):
-                nbytes = int(L.rk_stem_wgrad16_workspace_bytes(Fr, Cin, Cout, H, W))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                rc = L.rk_stem_wgrad3x3s2_bf16(dy.data_ptr(), x.data_ptr(), gw.data_ptr(), Fr, Cin, Cout, H, W, ws.data_ptr(),
-                                               nbytes, torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(rc, "rk_stem_wgrad3x3s2_bf16")
+            ws, nbytes = _native.workspace("rk_stem_wgrad16_workspace_bytes", dev, Fr, Cin, Cout, H, W)
+            _native.launch("rk_stem_wgrad3x3s2_bf16", dev, dy.data_ptr(), x.data_ptr(), gw.data_ptr(), Fr, Cin, Cout, H, W,
+                           ws.data_ptr(), nbytes)
         return gx, gw
 
 
@@ -998,8 +830,8 @@ def stem_conv(conv, x):
     sw = config.switches()
     if (sw.fused_train and sw.fused_bn and conv.training and torch.is_grad_enabled() and conv.out_channels <= 128
             and ((x.shape[2] // 2) * (x.shape[3] // 2)) % 4 == 0):
-        from .train_block import _attach_stats
+        from .fused_bn import attach_stats
 
         y, stats = _StemFunc.apply(x.contiguous(), conv.weight, True)
-        return _attach_stats(y, stats)
+        return attach_stats(y, stats)
     return _StemFunc.apply(x.contiguous(), conv.weight)

@@ -24,7 +24,8 @@ import logging
 import torch
 
 from . import _native, config, fin_status, rubiksnet_cuda
-from .fused_bn import _count_batch
+from .fused_bn import _count_batch, _finish_tiles, attach_stats, take_stats
+from .pointwise import _is_1x1
 
 __all__ = ["fused_train_block", "take_stats", "bn_relu_from_stats", "stats_fallbacks"]
 
@@ -71,51 +72,21 @@ def _side_stream(dev):
     return st
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def take_stats(x, channels, count):
-    """The tile statistics a producing GEMM attached to `x` (float4 [C][tiles]), if they describe exactly this tensor."""
-    st = getattr(x, "_rk_stats", None)
-    if st is None:
-        return None
-    # (tiles of 128 / 64 columns or a workgroup's column halves, by kernel generation: every tile carries its own count)
-    if (st.dim() != 3 or st.shape[0] != channels or st.shape[1] < 1 or st.shape[2] != 4 or st.device != x.device
-            or getattr(x, "_rk_stats_count", None) != count or getattr(x, "_rk_stats_version", None) != x._version):
-        return None
-    return st
-
-
-def _attach_stats(t, stats):
-    t._rk_stats = stats
-    t._rk_stats_count = t.numel() // t.shape[1]        # elements per channel the tiles add up to
-    t._rk_stats_version = t._version       # an in-place edit of the tensor invalidates them
-    return t
-
-
 def _tile_stats(L, x, Fr, C, P):
     J = int(L.rk_pw_tiles(Fr, P))
     st = torch.empty(C, J, 4, dtype=torch.float32, device=x.device)
-    _native.check(L.rk_bn_tile_stats_f32(x.data_ptr(), st.data_ptr(), Fr, C, P, _stream(x.device)), "rk_bn_tile_stats_f32")
+    _native.call("rk_bn_tile_stats_f32", x.data_ptr(), st.data_ptr(), Fr, C, P, _stream(x.device))
     return st
 
 
 def _finish(L, bn, stats, count, dev):
     """Tile partials -> (save_mean, save_invstd, a, b) of `bn`'s training forward; running statistics and
     num_batches_tracked updated exactly as nn.BatchNorm2d does."""
-    C = bn.num_features
-    out = torch.empty(8, C, dtype=torch.float32, device=dev)         # rows 0-3: mean, invstd, a, b; rows 4-7: [C][4] packed
     momentum, counter = _count_batch(bn)
     tracked = bn.training and bn.track_running_stats
     rm = bn.running_mean if tracked else None
     rv = bn.running_var if tracked else None
-    rc = L.rk_bn_finish_tiles_f32(stats.data_ptr(), stats.shape[1], count, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                  _ptr(rm), _ptr(rv), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                  out[3].data_ptr(), out[4].data_ptr(), C, float(bn.eps), float(momentum), _ptr(counter),
-                                  _stream(dev))
-    _native.check(rc, "rk_bn_finish_tiles_f32")
-    return out            # rows: mean, invstd, a, b, then (a, b, mean, invstd) per channel packed as [C][4]
+    return _finish_tiles(stats, count, bn.weight, bn.bias, rm, rv, momentum, bn.eps, _native.ptr(counter), dev, _stream(dev))
 
 
 def _bn_ok(bn):
@@ -124,9 +95,7 @@ def _bn_ok(bn):
 
 
 def _conv_ok(conv, stride):
-    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (stride, stride)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
+    return (_is_1x1(conv, stride) and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
             and max(conv.in_channels, conv.out_channels) <= _CMAX)
 
 
@@ -191,21 +160,18 @@ class _FusedTrainBlock(torch.autograd.Function):
                         sst = side.cuda_stream
                     if plan.stride == 2:
                         short = torch.empty(Fr, Cout, Ho, Wo, dtype=x.dtype, device=dev)
-                        _native.check(L.rk_pw_s2_forward_fused_f32(wsc.data_ptr(), x.data_ptr(), short.data_ptr(), Fr, Cin, Cout,
-                                                                   H, W, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, sst),
-                                      "rk_pw_s2_forward_fused_f32")
+                        _native.call("rk_pw_s2_forward_fused_f32", wsc.data_ptr(), x.data_ptr(), short.data_ptr(), Fr, Cin,
+                                     Cout, H, W, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, sst)
                     else:
                         short = torch.empty(Fr, Cout, H, W, dtype=x.dtype, device=dev)
-                        _native.check(L.rk_pw_gemm_fused_f32(wsc.data_ptr(), x.data_ptr(), None, short.data_ptr(), Fr, Cin, Cout,
-                                                             P, 1, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, None, None, 0, sst),
-                                      "rk_pw_gemm_fused_f32")
+                        _native.call("rk_pw_gemm_fused_f32", wsc.data_ptr(), x.data_ptr(), None, short.data_ptr(), Fr, Cin,
+                                     Cout, P, 1, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, None, None, 0, sst)
                 # conv2 on relu(bn1(x)), + the statistics of its output for bn2
                 z = torch.empty(Fr, Cmid, H, W, dtype=x.dtype, device=dev)
                 J = int(L.rk_pw_gemm_tiles(w2.data_ptr(), Fr, Cin, Cmid, P, 1))
                 stats2 = torch.empty(Cmid, J, 4, dtype=torch.float32, device=dev)
-                _native.check(L.rk_pw_gemm_stats_f32(w2.data_ptr(), x.data_ptr(), None, z.data_ptr(), Fr, Cin, Cmid, P, 1,
-                                                     bn1[2].data_ptr(), bn1[3].data_ptr(), 1, stats2.data_ptr(), J, st),
-                              "rk_pw_gemm_stats_f32")
+                _native.call("rk_pw_gemm_stats_f32", w2.data_ptr(), x.data_ptr(), None, z.data_ptr(), Fr, Cin, Cmid, P, 1,
+                             bn1[2].data_ptr(), bn1[3].data_ptr(), 1, stats2.data_ptr(), J, st)
                 bn2 = _finish(L, blk.bn2, stats2, Fr * P, dev)
                 # the shift of relu(bn2(z)), on [N, T, C, H, W] views of the same memory.  Fused (the kernels normalise the
                 # landed planes in LDS: the activation is never stored) where a fused kernel exists, else normalise + shift.
@@ -218,8 +184,8 @@ class _FusedTrainBlock(torch.autograd.Function):
                                                                      bool(plan.layer.quantize), s.view(N, plan.T, Cmid, Ho, Wo))
                 if rc == rubiksnet_cuda.UNSUPPORTED:
                     a2 = torch.empty_like(z)
-                    _native.check(L.rk_bn_apply_affine_f32(z.data_ptr(), bn2[2].data_ptr(), bn2[3].data_ptr(), a2.data_ptr(),
-                                                           Fr, Cmid, P, 1, st), "rk_bn_apply_affine_f32")
+                    _native.call("rk_bn_apply_affine_f32", z.data_ptr(), bn2[2].data_ptr(), bn2[3].data_ptr(), a2.data_ptr(),
+                                 Fr, Cmid, P, 1, st)
                     rubiksnet_cuda.rubiks_shift_3d_forward_float(a2.view(N, plan.T, Cmid, H, W), shift_c, s3, pd,
                                                                  bool(plan.layer.quantize), s.view(N, plan.T, Cmid, Ho, Wo))
                 # SE gate (Small tier, backbone.py:56-71, :131-132): squeeze = one pass over s, the two tiny Linear layers in
@@ -227,7 +193,7 @@ class _FusedTrainBlock(torch.autograd.Function):
                 se_q = se_h = se_g = s_in = None
                 if wse1 is not None:
                     se_q = torch.empty(Fr, Cmid, dtype=torch.float32, device=dev)
-                    _native.check(L.rk_se_squeeze_f32(s.data_ptr(), se_q.data_ptr(), Fr, Cmid, Po, st), "rk_se_squeeze_f32")
+                    _native.call("rk_se_squeeze_f32", s.data_ptr(), se_q.data_ptr(), Fr, Cmid, Po, st)
                     Cr = wse1.shape[0]
                     se_h = torch.empty(Fr, Cr, dtype=torch.float32, device=dev)
                     se_g = torch.empty(Fr, Cmid, dtype=torch.float32, device=dev)
@@ -239,8 +205,7 @@ class _FusedTrainBlock(torch.autograd.Function):
                     else:
                         _native.check(rc, "rk_se_mlp_forward_f32")
                     s_in = torch.empty_like(s)
-                    _native.check(L.rk_se_scale_f32(s.data_ptr(), se_g.data_ptr(), s_in.data_ptr(), Fr, Cmid, Po, st),
-                                  "rk_se_scale_f32")
+                    _native.call("rk_se_scale_f32", s.data_ptr(), se_g.data_ptr(), s_in.data_ptr(), Fr, Cmid, Po, st)
                 conv3_in = s_in if s_in is not None else s
                 # conv3 + shortcut, + the statistics of the block's output for whoever normalises it next
                 if side is not None:
@@ -248,9 +213,8 @@ class _FusedTrainBlock(torch.autograd.Function):
                 out = torch.empty(Fr, Cout, Ho, Wo, dtype=x.dtype, device=dev)
                 Jo = int(L.rk_pw_gemm_tiles(w3.data_ptr(), Fr, Cmid, Cout, Po, 1))
                 stats_out = torch.empty(Cout, Jo, 4, dtype=torch.float32, device=dev)
-                _native.check(L.rk_pw_gemm_stats_f32(w3.data_ptr(), conv3_in.data_ptr(), short.data_ptr(), out.data_ptr(), Fr, Cmid,
-                                                     Cout, Po, 1, None, None, 0, stats_out.data_ptr(), Jo, st),
-                              "rk_pw_gemm_stats_f32")
+                _native.call("rk_pw_gemm_stats_f32", w3.data_ptr(), conv3_in.data_ptr(), short.data_ptr(), out.data_ptr(), Fr,
+                             Cmid, Cout, Po, 1, None, None, 0, stats_out.data_ptr(), Jo, st)
             finally:
                 # an exception between the fork and the join must not let the allocator hand out buffers the side
                 # stream still uses: the join always runs
@@ -293,8 +257,7 @@ class _FusedTrainBlock(torch.autograd.Function):
             keep = []                                       # buffers the side stream uses: alive until the streams have joined
 
             def wgrad_ws(K, M, Pn):
-                nbytes = int(L.rk_pw_wgrad_workspace_bytes(Fr, K, M, Pn))
-                buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+                buf, nbytes = _native.workspace("rk_pw_wgrad_workspace_bytes", dev, Fr, K, M, Pn)
                 keep.append(buf)
                 return buf, nbytes
 
@@ -308,22 +271,20 @@ class _FusedTrainBlock(torch.autograd.Function):
             try:
                 # conv3: d(s) = W3^T dout, d(W3) = dout s^T
                 ds = torch.empty_like(s)
-                _native.check(L.rk_pw_gemm_f32(w3.data_ptr(), dout.data_ptr(), None, ds.data_ptr(), Fr, Cout, Cmid, Po, 0, st),
-                              "rk_pw_gemm_f32")
+                _native.call("rk_pw_gemm_f32", w3.data_ptr(), dout.data_ptr(), None, ds.data_ptr(), Fr, Cout, Cmid, Po, 0, st)
                 dw3 = None
                 if need[8]:
                     dw3 = torch.empty_like(w3)
                     ws, nb = wgrad_ws(Cmid, Cout, Po)
-                    _native.check(L.rk_pw_wgrad_f32(dout.data_ptr(), (s_in if ctx.has_se else s).data_ptr(), dw3.data_ptr(), Fr,
-                                                    Cmid, Cout, Po, ws.data_ptr(), nb, wg_stream()), "rk_pw_wgrad_f32")
+                    _native.call("rk_pw_wgrad_f32", dout.data_ptr(), (s_in if ctx.has_se else s).data_ptr(), dw3.data_ptr(), Fr,
+                                 Cmid, Cout, Po, ws.data_ptr(), nb, wg_stream())
                 if ctx.has_se:
                     # SE backward: ds (so far d(s * gate)) -> d(s) = ds gate + d(squeeze) / HW, d(gate) = sum_hw(ds s) in one
                     # pass over (ds, s); the two Linear layers and their activations by hand (a few [F, C]-sized kernels)
                     # (4 tensor passes: the reduction alone, then d(s) with the squeeze's share added in the same pass --
                     # scale_backward + a broadcast add were 5)
                     dgate = torch.empty_like(se_g)
-                    _native.check(L.rk_se_dgate_f32(ds.data_ptr(), s.data_ptr(), dgate.data_ptr(), Fr, Cmid, Po, st),
-                                  "rk_se_dgate_f32")
+                    _native.call("rk_se_dgate_f32", ds.data_ptr(), s.data_ptr(), dgate.data_ptr(), Fr, Cmid, Po, st)
                     Cr = wse1.shape[0]
                     dpre2 = torch.empty_like(se_g)
                     dpre1 = torch.empty_like(se_h)
@@ -341,8 +302,8 @@ class _FusedTrainBlock(torch.autograd.Function):
                     else:
                         _native.check(rc, "rk_se_mlp_backward_f32")
                     dsg = torch.empty_like(s)
-                    _native.check(L.rk_se_scale_add_f32(ds.data_ptr(), se_g.data_ptr(), dq.data_ptr(), 1.0 / float(Po),
-                                                        dsg.data_ptr(), Fr, Cmid, Po, st), "rk_se_scale_add_f32")
+                    _native.call("rk_se_scale_add_f32", ds.data_ptr(), se_g.data_ptr(), dq.data_ptr(), 1.0 / float(Po),
+                                 dsg.data_ptr(), Fr, Cmid, Po, st)
                     ds = dsg
                 # the shift and bn2: d(shift), and d(z) = bn2 + ReLU backward of d(a2).  Fused: the shift backward reads z,
                 # masks its d(x) with the ReLU and reduces bn2's sums in the same launch (dg2, db2, k12); one d(x) pass finishes.
@@ -360,25 +321,22 @@ class _FusedTrainBlock(torch.autograd.Function):
                         dzm.view(N, plan.T, Cmid, H, W), dshift, k12b, dg2, db2, plan.layer.normalize_grad, plan.t_factor,
                         bool(plan.layer.quantize))
                     if rc == 0:
-                        _native.check(L.rk_bn_bwd_dx_pre_f32(dzm.data_ptr(), z.data_ptr(), g2.data_ptr(), bn2[0].data_ptr(),
-                                                             bn2[1].data_ptr(), k12b.data_ptr(), None, dz.data_ptr(), Fr, Cmid,
-                                                             P, st), "rk_bn_bwd_dx_pre_f32")
+                        _native.call("rk_bn_bwd_dx_pre_f32", dzm.data_ptr(), z.data_ptr(), g2.data_ptr(), bn2[0].data_ptr(),
+                                     bn2[1].data_ptr(), k12b.data_ptr(), None, dz.data_ptr(), Fr, Cmid, P, st)
                     else:                                     # (no fused backward for a shape the forward took: recompute a2)
                         a2 = torch.empty_like(z)
-                        _native.check(L.rk_bn_apply_affine_f32(z.data_ptr(), bn2[2].data_ptr(), bn2[3].data_ptr(),
-                                                               a2.data_ptr(), Fr, Cmid, P, 1, st), "rk_bn_apply_affine_f32")
+                        _native.call("rk_bn_apply_affine_f32", z.data_ptr(), bn2[2].data_ptr(), bn2[3].data_ptr(),
+                                     a2.data_ptr(), Fr, Cmid, P, 1, st)
                 if rc != 0:
                     da2 = torch.empty_like(a2)
                     rubiksnet_cuda.rubiks_shift_3d_backward_float(
                         a2.view(N, plan.T, Cmid, H, W), shift, ds.view(N, plan.T, Cmid, Ho, Wo), s3, pd,
                         da2.view(N, plan.T, Cmid, H, W), dshift, plan.layer.normalize_grad, plan.t_factor,
                         bool(plan.layer.quantize))
-                    nbn = int(L.rk_bn_workspace_bytes(Fr, Cmid, P))
-                    wsb = torch.empty(max(nbn, 1), dtype=torch.uint8, device=dev)
-                    _native.check(L.rk_bn_relu_backward_f32(da2.data_ptr(), z.data_ptr(), g2.data_ptr(), b2.data_ptr(),
-                                                            bn2[0].data_ptr(), bn2[1].data_ptr(), None, dz.data_ptr(),
-                                                            dg2.data_ptr(), db2.data_ptr(), Fr, Cmid, P, 1, wsb.data_ptr(), nbn,
-                                                            st), "rk_bn_relu_backward_f32")
+                    wsb, nbn = _native.workspace("rk_bn_workspace_bytes", dev, Fr, Cmid, P)
+                    _native.call("rk_bn_relu_backward_f32", da2.data_ptr(), z.data_ptr(), g2.data_ptr(), b2.data_ptr(),
+                                 bn2[0].data_ptr(), bn2[1].data_ptr(), None, dz.data_ptr(), dg2.data_ptr(), db2.data_ptr(), Fr,
+                                 Cmid, P, 1, wsb.data_ptr(), nbn, st)
                     del da2
                 if not need[7]:
                     dshift = None
@@ -387,48 +345,43 @@ class _FusedTrainBlock(torch.autograd.Function):
                 if not plan.identity:
                     res = torch.empty_like(x)
                     if plan.stride == 2:
-                        _native.check(L.rk_pw_s2_dgrad_f32(wsc.data_ptr(), dout.data_ptr(), res.data_ptr(), Fr, Cin, Cout, H, W,
-                                                           st), "rk_pw_s2_dgrad_f32")
+                        _native.call("rk_pw_s2_dgrad_f32", wsc.data_ptr(), dout.data_ptr(), res.data_ptr(), Fr, Cin, Cout, H, W,
+                                     st)
                     else:
-                        _native.check(L.rk_pw_gemm_f32(wsc.data_ptr(), dout.data_ptr(), None, res.data_ptr(), Fr, Cout, Cin, P,
-                                                       0, st), "rk_pw_gemm_f32")
+                        _native.call("rk_pw_gemm_f32", wsc.data_ptr(), dout.data_ptr(), None, res.data_ptr(), Fr, Cout, Cin, P,
+                                     0, st)
                     if need[9]:
                         dwsc = torch.empty_like(wsc)
                         ws, nb = wgrad_ws(Cin, Cout, Po)
                         if plan.stride == 2:
-                            _native.check(L.rk_pw_s2_wgrad_pro_f32(dout.data_ptr(), x.data_ptr(), dwsc.data_ptr(), Fr, Cin, Cout,
-                                                                   H, W, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, ws.data_ptr(),
-                                                                   nb, wg_stream()), "rk_pw_s2_wgrad_pro_f32")
+                            _native.call("rk_pw_s2_wgrad_pro_f32", dout.data_ptr(), x.data_ptr(), dwsc.data_ptr(), Fr, Cin,
+                                         Cout, H, W, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, ws.data_ptr(), nb, wg_stream())
                         else:
-                            _native.check(L.rk_pw_wgrad_pro_f32(dout.data_ptr(), x.data_ptr(), dwsc.data_ptr(), Fr, Cin, Cout, P,
-                                                                bn1[2].data_ptr(), bn1[3].data_ptr(), 1, ws.data_ptr(), nb,
-                                                                wg_stream()), "rk_pw_wgrad_pro_f32")
+                            _native.call("rk_pw_wgrad_pro_f32", dout.data_ptr(), x.data_ptr(), dwsc.data_ptr(), Fr, Cin, Cout,
+                                         P, bn1[2].data_ptr(), bn1[3].data_ptr(), 1, ws.data_ptr(), nb, wg_stream())
                 # conv2: d(W2) from (dz, relu(bn1(x)) recomputed); d(input) masked by the ReLU, + bn1's reduction sums
                 dw2 = None
                 if need[4]:
                     dw2 = torch.empty_like(w2)
                     ws, nb = wgrad_ws(Cin, Cmid, P)
-                    _native.check(L.rk_pw_wgrad_pro_f32(dz.data_ptr(), x.data_ptr(), dw2.data_ptr(), Fr, Cin, Cmid, P,
-                                                        bn1[2].data_ptr(), bn1[3].data_ptr(), 1, ws.data_ptr(), nb, wg_stream()),
-                                  "rk_pw_wgrad_pro_f32")
+                    _native.call("rk_pw_wgrad_pro_f32", dz.data_ptr(), x.data_ptr(), dw2.data_ptr(), Fr, Cin, Cmid, P,
+                                 bn1[2].data_ptr(), bn1[3].data_ptr(), 1, ws.data_ptr(), nb, wg_stream())
                 J = int(L.rk_pw_gemm_tiles(w2.data_ptr(), Fr, Cmid, Cin, P, 0))
                 bred = torch.empty(Cin, J, 2, dtype=torch.float32, device=dev)
                 dzm = res if res is not None else torch.empty_like(x)             # (the residual may alias the result)
-                _native.check(L.rk_pw_gemm_bnbwd_f32(w2.data_ptr(), dz.data_ptr(), _ptr(res), dzm.data_ptr(), Fr, Cmid, Cin, P,
-                                                     0, x.data_ptr(), bn1[4].data_ptr(), bred.data_ptr(), J, st),
-                              "rk_pw_gemm_bnbwd_f32")
+                _native.call("rk_pw_gemm_bnbwd_f32", w2.data_ptr(), dz.data_ptr(), _native.ptr(res), dzm.data_ptr(), Fr, Cmid, Cin, P,
+                             0, x.data_ptr(), bn1[4].data_ptr(), bred.data_ptr(), J, st)
                 k12 = torch.empty(2, Cin, dtype=torch.float32, device=dev)
                 dg1 = torch.empty(Cin, dtype=torch.float32, device=dev)
                 db1 = torch.empty(Cin, dtype=torch.float32, device=dev)
-                _native.check(L.rk_bn_bwd_finish_tiles_f32(bred.data_ptr(), J, Fr * P, k12.data_ptr(), dg1.data_ptr(),
-                                                           db1.data_ptr(), Cin, st), "rk_bn_bwd_finish_tiles_f32")
+                _native.call("rk_bn_bwd_finish_tiles_f32", bred.data_ptr(), J, Fr * P, k12.data_ptr(), dg1.data_ptr(),
+                             db1.data_ptr(), Cin, st)
                 dx = None
                 if need[0]:
                     dx = torch.empty_like(x)
                     skip = dout if plan.identity else None                        # identity shortcut: out = ... + x
-                    _native.check(L.rk_bn_bwd_dx_pre_f32(dzm.data_ptr(), x.data_ptr(), g1.data_ptr(), bn1[0].data_ptr(),
-                                                         bn1[1].data_ptr(), k12.data_ptr(), _ptr(skip), dx.data_ptr(), Fr, Cin,
-                                                         P, st), "rk_bn_bwd_dx_pre_f32")
+                    _native.call("rk_bn_bwd_dx_pre_f32", dzm.data_ptr(), x.data_ptr(), g1.data_ptr(), bn1[0].data_ptr(),
+                                 bn1[1].data_ptr(), k12.data_ptr(), _native.ptr(skip), dx.data_ptr(), Fr, Cin, P, st)
             finally:
                 if side is not None:
                     cur.wait_stream(side)                   # always: gradients complete (and the side stream's buffers
@@ -481,7 +434,7 @@ def fused_train_block(block, x):
     out, stats_out = _FusedTrainBlock.apply(
         x, stats_in, block.bn1.weight, block.bn1.bias, block.conv2.weight, block.bn2.weight, block.bn2.bias,
         cfg[0].shift, block.conv3.weight, None if identity else block.shortcut.weight, se1, se2, plan)
-    return _attach_stats(out, stats_out)
+    return attach_stats(out, stats_out)
 
 
 def bn_relu_from_stats(bn, x, relu=True):
@@ -510,8 +463,8 @@ class _BNFromStats(torch.autograd.Function):
         with torch.cuda.device(dev):
             fin = _finish(L, bn, stats, Fr * H * W, dev)
             y = torch.empty_like(x)
-            _native.check(L.rk_bn_apply_affine_f32(x.data_ptr(), fin[2].data_ptr(), fin[3].data_ptr(), y.data_ptr(), Fr, C,
-                                                   H * W, int(relu), _stream(dev)), "rk_bn_apply_affine_f32")
+            _native.call("rk_bn_apply_affine_f32", x.data_ptr(), fin[2].data_ptr(), fin[3].data_ptr(), y.data_ptr(), Fr, C,
+                         H * W, int(relu), _stream(dev))
         ctx.save_for_backward(x, weight, bias, fin)
         ctx.relu = relu
         return y
@@ -519,18 +472,14 @@ class _BNFromStats(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight, bias, fin = ctx.saved_tensors
-        L = _native.lib()
         dev = x.device
         Fr, C, H, W = x.shape
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         dg = torch.empty(C, dtype=torch.float32, device=dev)
         db = torch.empty(C, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            nb = int(L.rk_bn_workspace_bytes(Fr, C, H * W))
-            ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-            _native.check(L.rk_bn_relu_backward_f32(dy.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                                    fin[0].data_ptr(), fin[1].data_ptr(), None, dx.data_ptr(), dg.data_ptr(),
-                                                    db.data_ptr(), Fr, C, H * W, int(ctx.relu), ws.data_ptr(), nb,
-                                                    _stream(dev)), "rk_bn_relu_backward_f32")
+        ws, nb = _native.workspace("rk_bn_workspace_bytes", dev, Fr, C, H * W)
+        _native.launch("rk_bn_relu_backward_f32", dev, dy.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                       fin[0].data_ptr(), fin[1].data_ptr(), None, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), Fr, C, H * W,
+                       int(ctx.relu), ws.data_ptr(), nb)
         return dx, None, dg, db, None, None

@@ -306,3 +306,12 @@ def test_bn_tshift_fusion_declines_off_device():
     with torch.no_grad():
         assert bn_relu_tshift_skip(bn.train(), shift, x) is None       # no gradient wanted
     assert bn_relu_tshift_skip(bn, AttentionShift(4), x) is None       # taps not created yet
+
+
+def test_checked_call_names_the_entry_point():
+    """_native.call raises with the name of the entry point it called (rk_pw_gemm_f32 returns its null-pointer status
+    before any device call)."""
+    from rubiksnet_amd import _native
+
+    with pytest.raises(_native.RubiksHipError, match="rk_pw_gemm_f32"):
+        _native.call("rk_pw_gemm_f32", None, None, None, None, 1, 2, 2, 4, 1, None)
