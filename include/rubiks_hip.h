@@ -745,7 +745,8 @@ enum {
     RK_JPEG_TRUNCATED = 4,    /* bits wanted past the segment's end or past a marker */
     RK_JPEG_BAD_RESTART = 5,  /* RSTn missing or out of order */
     RK_JPEG_TRAILING = 6,     /* whole bytes left over, or pad bits that are not ones */
-    RK_JPEG_BAD_VALUE = 7     /* a magnitude category or DC value outside what 8-bit baseline can hold */
+    RK_JPEG_BAD_VALUE = 7,    /* a magnitude category or DC value outside what 8-bit baseline can hold */
+    RK_JPEG_BAD_INDEX = 8     /* a scan index (below) that does not fit the frame or does not tile its stream */
 };
 #define RK_JPEG_MAX_SIDE 16384
 typedef struct rk_jpeg_frame {
@@ -772,6 +773,55 @@ size_t rk_jpeg_workspace_bytes(const rk_jpeg_frame* frames_host, int n);
 int rk_jpeg_decode_u8(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
                       const unsigned short* qtabs, const rk_jpeg_huff* htabs, int nq, int nh, int n, unsigned char* rgb,
                       long long rgb_bytes, void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream);
+
+/* ---- resident JPEG frames decoded by scan index (rk_jpeg.hip) ----
+ * A baseline scan can only be entered where the bit position and the DC predictors are known.  A set that stays on the
+ * device (streams, records and tables laid out as above; a resident record's rgb_off is not used) is walked ONCE by
+ * rk_jpeg_build_index, which remembers that state every seg_mcus[i] MCUs of frame i; every later decode of a frame
+ * (rk_jpeg_decode_indexed_u8) then runs one Huffman chain per segment instead of one per frame.
+ *   entry      the state at the top of MCU m's iteration, before its restart handling: bit_pos = 8 * (offset in the
+ *              frame's segment of the raw byte that holds the next unread bit; FF 00 counts as two raw bytes and the bit
+ *              lives in the FF) + (bit in that byte, 0 = most significant) -- the marker's FF, or stream_len, bit 0, when
+ *              everything up to a marker or the end is used up -- and the three DC predictors.  The restart state follows
+ *              from m and restart_interval and is not stored.
+ *   seg_mcus   device int [n]: E_i >= 1; segment s of frame i covers MCUs [s * E_i, min((s + 1) * E_i, nmcu_i))
+ *   entry_off  device long long [n + 1]: the exclusive sum of the frames' segment counts ceil(nmcu_i / E_i) (host-made)
+ *   entries    device [n_entries]: frame i's entries at [entry_off[i], entry_off[i + 1])
+ * rk_jpeg_build_index: one wave per frame, n at most 65535 per call (a larger set is built in chunks: pass the chunk's
+ * frames, seg_mcus, entry_off and status; entry_off stays absolute).  A record is checked from its own fields first
+ * (RK_JPEG_BAD_RECORD), then its row of the index (E_i < 1, a range that is not ceil(nmcu / E) long or leaves
+ * [0, n_entries]: RK_JPEG_BAD_INDEX), before anything of the frame is read; status[i] is otherwise the code
+ * rk_jpeg_decode_u8 would give the frame, status[n] the count of non-zero codes.  Entries of a failed frame are undefined.
+ * rk_jpeg_decode_indexed_u8: decodes resident frames pick[j] (device int [m]) to rgb + rgb_off[j] (device long long [m]);
+ * the same frame may be picked twice.  max_segments: at least the largest segment count among the picked frames (the
+ * host knows every geometry; a picked frame with more fails with RK_JPEG_BAD_INDEX).  build_status: the build's
+ * status array; a frame whose build code is not 0 is not read and gets that code.  A pick outside [0, n) is
+ * RK_JPEG_BAD_RECORD.  Entries are untrusted device data: a segment checks its entry before its first read (bit_pos
+ * outside [0, 8 * stream_len], a predictor outside +-2047, a non-zero entry 0) and, after its last MCU, that the reader
+ * stands exactly at the next entry's bit_pos with the next entry's predictors (the last segment: at the end of the
+ * stream) -- so the segments tile the stream -- and fails with RK_JPEG_BAD_INDEX otherwise.  status [m + 1]: per picked
+ * frame the code of its lowest failing segment (a plain pass over a per-segment table in the workspace: no atomics, the
+ * same code on every run), [m] the count.  Everything else is as rk_jpeg_decode_u8 documents: failed frames are zeroed
+ * where their range is valid, no read outside the arenas, no allocation, no host wait, capturable; seven launches.
+ * m and max_segments in [1, 65535].  Each segment is one wave in a workgroup of its own.                            */
+typedef struct rk_jpeg_entry {
+    long long bit_pos;
+    short pred[3];
+    short reserved;
+} rk_jpeg_entry;                    /* 16 bytes */
+int rk_jpeg_build_index(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                        const rk_jpeg_huff* htabs, int nq, int nh, int n, const int* seg_mcus, const long long* entry_off,
+                        rk_jpeg_entry* entries, long long n_entries, int* status, rk_stream_t stream);
+/* Workspace of one indexed decode, from HOST copies of the resident records and of pick: the m gathered records, the
+ * per-segment table, then rk_jpeg_workspace_bytes of the picked records.  0 for a NULL table, m < 1 or max_segments < 1;
+ * a pick outside [0, n) takes no frame region. */
+size_t rk_jpeg_indexed_workspace_bytes(const rk_jpeg_frame* frames_host, int n, const int* pick_host, int m, int max_segments);
+int rk_jpeg_decode_indexed_u8(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                              const unsigned short* qtabs, const rk_jpeg_huff* htabs, int nq, int nh, int n,
+                              const rk_jpeg_entry* entries, long long n_entries, const long long* entry_off,
+                              const int* seg_mcus, const int* build_status, const int* pick, const long long* rgb_off, int m,
+                              int max_segments, unsigned char* rgb, long long rgb_bytes, void* workspace,
+                              size_t workspace_bytes, int* status, rk_stream_t stream);
 
 /* ---- squeeze-and-excitation gate of RubiksNet-Small -- widening row f3 of SURVEY 8(f) --------------
  * SELayer (rubiksnet/backbone.py:56-71): y = x * sigmoid(W2 relu(W1 mean_hw(x))).  x, y, dy, dx [F, C, P];

@@ -165,6 +165,14 @@ for _sfx in ("f32", "bf16", "f16"):
 # rgb, rgb_bytes, workspace, workspace_bytes, status, stream
 SIGNATURES["rk_jpeg_workspace_bytes"] = (_sz, [_p, _i])
 SIGNATURES["rk_jpeg_decode_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _p, ctypes.c_longlong, _p, _sz, _p, _p])
+# resident frames decoded by scan index: streams, stream_bytes, frames, htabs, nq, nh, n, seg_mcus, entry_off, entries,
+# n_entries, status, stream / host frame table, n, host pick, m, max_segments -> bytes / streams, stream_bytes, frames, qtabs,
+# htabs, nq, nh, n, entries, n_entries, entry_off, seg_mcus, build_status, pick, rgb_off, m, max_segments, rgb, rgb_bytes,
+# workspace, workspace_bytes, status, stream
+SIGNATURES["rk_jpeg_build_index"] = (_i, [_p, ctypes.c_longlong, _p, _p, _i, _i, _i, _p, _p, _p, ctypes.c_longlong, _p, _p])
+SIGNATURES["rk_jpeg_indexed_workspace_bytes"] = (_sz, [_p, _i, _p, _i, _i])
+SIGNATURES["rk_jpeg_decode_indexed_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _p, ctypes.c_longlong, _p, _p, _p, _p,
+                                                _p, _i, _i, _p, ctypes.c_longlong, _p, _sz, _p, _p])
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw

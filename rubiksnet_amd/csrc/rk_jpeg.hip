@@ -16,6 +16,15 @@
 //   k_jpeg_count    status[n] = frames with a non-zero code
 //
 // The launcher knows n and the byte counts only, so every grid is sized by n and strides over a frame's work.
+//
+// A resident set (rk_jpeg_build_index, rk_jpeg_decode_indexed_u8) replaces the one chain per frame by one per segment:
+//
+//   k_jpeg_index        one wave per frame, once: the same walk with no coefficient stored, the reader's position and the
+//                       DC predictors written every E MCUs
+//   k_jpeg_gather       the picked records, with their places in the RGB arena, into the head of the workspace, so that
+//                       plan, IDCT, colour and count run on them unchanged
+//   k_jpeg_entropy_seg  one wave (and one workgroup) per segment: resumes at its entry, must end at the next one
+//   k_jpeg_seg_status   a frame's code = that of its lowest failing segment
 #include "rk_common.hpp"
 #include "rk_jpeg_core.hpp"
 
@@ -23,6 +32,7 @@ namespace rk {
 namespace {
 
 constexpr int kJpegWindow = 2048;       // bytes of a frame's stream staged in LDS at a time
+constexpr int kSegWindow = 1024;        // the same for one segment of a frame: tables + window stay under 160 KB / 16 per CU
 constexpr int kIdctSlices = 16;         // workgroups per frame in k_jpeg_idct
 constexpr int kColourSlices = 32;       // workgroups per frame in k_jpeg_colour
 
@@ -48,21 +58,23 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_plan(const rk_jpeg_frame* __res
 }
 
 // The frame's segment through an LDS window; every lane of the wave calls byte() with the same position.
-struct WindowSrc {
+template <int kWindow>
+struct WindowSrcT {
     const unsigned char* g;         // the segment in global memory
     unsigned char* win;
     long long base, len;
     int lane;
     __device__ __forceinline__ int byte(long long p) {
-        if (p < base || p >= base + kJpegWindow) {
+        if (p < base || p >= base + kWindow) {
             __syncthreads();        // one wave per workgroup: orders the LDS traffic, cannot wait on anyone
             base = p;
-            for (int k = lane; k < kJpegWindow; k += kWave) win[k] = (base + k < len) ? g[base + k] : (unsigned char)0;
+            for (int k = lane; k < kWindow; k += kWave) win[k] = (base + k < len) ? g[base + k] : (unsigned char)0;
             __syncthreads();
         }
         return win[(int)(p - base)];
     }
 };
+typedef WindowSrcT<kJpegWindow> WindowSrc;
 
 // Lane p holds coefficient p (natural order) of the block being decoded; `zigzag` is that coefficient's place in the
 // scan, looked up once per lane, so that a decoded coefficient costs one compare and no table access.
@@ -105,6 +117,134 @@ __global__ __launch_bounds__(kWave) void k_jpeg_entropy(const unsigned char* __r
     LaneSink sink{reinterpret_cast<short*>(ws + reinterpret_cast<const long long*>(ws)[i]), lane, zigzag, 0};
     const int rc = rkjpeg::decode_scan(f, g, src, tabs, sink);
     if (lane == 0) status[i] = rc;
+}
+
+// ---------------------------------------------------------------------------------------------- the scan index
+// The frame's six tables into LDS, as k_jpeg_entropy loads them (one wave; the caller syncs).
+__device__ __forceinline__ void load_tables(const rk_jpeg_frame& f, int ncomp, const rk_jpeg_huff* __restrict__ htabs,
+                                            rk_jpeg_huff* tabs, int lane) {
+    constexpr int kWords = sizeof(rk_jpeg_huff) / 4;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (c >= ncomp) break;
+        const unsigned* d = reinterpret_cast<const unsigned*>(htabs + f.dc[c]);
+        const unsigned* a = reinterpret_cast<const unsigned*>(htabs + f.ac[c]);
+        for (int k = lane; k < kWords; k += kWave) {
+            reinterpret_cast<unsigned*>(&tabs[c])[k] = d[k];
+            reinterpret_cast<unsigned*>(&tabs[3 + c])[k] = a[k];
+        }
+    }
+}
+
+// One wave per resident frame: the record and its row of the index checked from their own fields, then the one
+// sequential walk the frame ever gets, which stores no coefficient and writes the entry of every E-th MCU.
+__global__ __launch_bounds__(kWave) void k_jpeg_index(const unsigned char* __restrict__ streams, long long stream_bytes,
+                                                      const rk_jpeg_frame* __restrict__ frames,
+                                                      const rk_jpeg_huff* __restrict__ htabs, int nq, int nh,
+                                                      const int* __restrict__ seg_mcus, const long long* __restrict__ entry_off,
+                                                      rk_jpeg_entry* __restrict__ entries, long long n_entries,
+                                                      int* __restrict__ status) {
+    __shared__ rk_jpeg_huff tabs[6];
+    __shared__ unsigned char win[kJpegWindow];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const rk_jpeg_frame f = frames[i];
+    int rc = rkjpeg::check_resident(f, stream_bytes, nq, nh);
+    rkjpeg::Geometry g;
+    const int E = seg_mcus[i];
+    const long long first = entry_off[i], last = entry_off[i + 1];
+    if (rc == RK_JPEG_OK) {
+        rkjpeg::geometry(f, g);
+        if (!rkjpeg::index_row_ok(g, E, first, last, n_entries)) rc = RK_JPEG_BAD_INDEX;
+    }
+    if (rc != RK_JPEG_OK) {                             // uniform: nothing of the frame is read
+        if (lane == 0) status[i] = rc;
+        return;
+    }
+    load_tables(f, g.ncomp, htabs, tabs, lane);
+    __syncthreads();
+    WindowSrc src{streams + f.stream_off, win, -(long long)kJpegWindow - 1, f.stream_len, lane};
+    rc = rkjpeg::record_index(f, g, src, tabs, E, entries + first, lane == 0);
+    if (lane == 0) status[i] = rc;
+}
+
+// The m picked records, each with its own place in the RGB arena, into the head of the workspace: from here on the
+// plan / IDCT / colour / count kernels run on them as on any frame table.  A pick outside the set gives a zero record,
+// which k_jpeg_plan refuses and k_jpeg_colour has no range for.
+__global__ __launch_bounds__(kBlock) void k_jpeg_gather(const rk_jpeg_frame* __restrict__ frames, int n,
+                                                        const int* __restrict__ pick, const long long* __restrict__ rgb_off,
+                                                        int m, rk_jpeg_frame* __restrict__ out) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const int p = pick[j];
+    rk_jpeg_frame f = {};
+    if (p >= 0 && p < n) {
+        f = frames[p];
+        f.rgb_off = rgb_off[j];
+    }
+    out[j] = f;
+}
+
+// Grid (m, max_segments), one wave per segment, ONE WAVE PER WORKGROUP: WindowSrc::byte holds barriers inside
+// data-dependent control flow, which is safe only while no second wave exists to wait for.  Segment s of picked frame
+// j resumes at its entry, decodes its MCUs into the frame's coefficient region and checks that it ends at the next
+// entry; its code goes to segs[j * max_segments + s].  Blocks beyond the frame's segment count leave at once; a frame
+// the plan or the index build refused, or whose index row does not fit, is not read (k_jpeg_seg_status gives it its code).
+__global__ __launch_bounds__(kWave) void k_jpeg_entropy_seg(const unsigned char* __restrict__ streams,
+                                                            const rk_jpeg_frame* __restrict__ gathered,
+                                                            const rk_jpeg_huff* __restrict__ htabs,
+                                                            const rk_jpeg_entry* __restrict__ entries, long long n_entries,
+                                                            const long long* __restrict__ entry_off,
+                                                            const int* __restrict__ seg_mcus, const int* __restrict__ build_status,
+                                                            const int* __restrict__ pick, unsigned char* __restrict__ ws,
+                                                            const int* __restrict__ status, int* __restrict__ segs) {
+    __shared__ rk_jpeg_huff tabs[6];
+    __shared__ unsigned char win[kSegWindow];
+    const int j = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
+    if (status[j] != RK_JPEG_OK) return;                // the record is invalid (a pick outside the set included)
+    const int p = pick[j];
+    if (build_status[p] != RK_JPEG_OK) return;
+    const rk_jpeg_frame f = gathered[j];
+    rkjpeg::Geometry g;
+    rkjpeg::geometry(f, g);
+    const int E = seg_mcus[p];
+    const long long first = entry_off[p], last = entry_off[p + 1];
+    if (!rkjpeg::index_row_ok(g, E, first, last, n_entries) || last - first > gridDim.y || s >= last - first) return;
+    load_tables(f, g.ncomp, htabs, tabs, lane);
+    __syncthreads();
+    WindowSrcT<kSegWindow> src{streams + f.stream_off, win, -(long long)kSegWindow - 1, f.stream_len, lane};
+    int zigzag = 0;
+    for (int k = 0; k < 64; ++k) zigzag = rkjpeg::natural_of(k) == lane ? k : zigzag;
+    LaneSink sink{reinterpret_cast<short*>(ws + reinterpret_cast<const long long*>(ws)[j]), lane, zigzag, 0};
+    const long long nmcu = (long long)g.mcux * g.mcuy, m_begin = (long long)s * E;
+    const long long m_end = m_begin + E < nmcu ? m_begin + E : nmcu;
+    const rk_jpeg_entry entry = entries[first + s];
+    const rk_jpeg_entry next = entries[first + (s + 1 < last - first ? s + 1 : s)];     // the last segment does not look at it
+    const int rc = rkjpeg::decode_span(f, g, src, tabs, sink, entry, m_begin, m_end, &next);
+    if (lane == 0) segs[(long long)j * gridDim.y + s] = rc;
+}
+
+// status[j] of a picked frame the plan accepted: the build's code where the build refused the frame, RK_JPEG_BAD_INDEX
+// where its index row does not fit, else the code of its lowest failing segment -- a plain pass, the same code on every run.
+__global__ __launch_bounds__(kBlock) void k_jpeg_seg_status(const rk_jpeg_frame* __restrict__ gathered, long long n_entries,
+                                                            const long long* __restrict__ entry_off,
+                                                            const int* __restrict__ seg_mcus, const int* __restrict__ build_status,
+                                                            const int* __restrict__ pick, const int* __restrict__ segs, int m,
+                                                            int max_segments, int* __restrict__ status) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m || status[j] != RK_JPEG_OK) return;
+    const int p = pick[j];
+    int rc = build_status[p];
+    if (rc == RK_JPEG_OK) {
+        rkjpeg::Geometry g;
+        rkjpeg::geometry(gathered[j], g);
+        const long long first = entry_off[p], last = entry_off[p + 1];
+        if (!rkjpeg::index_row_ok(g, seg_mcus[p], first, last, n_entries) || last - first > max_segments) {
+            rc = RK_JPEG_BAD_INDEX;
+        } else {
+            for (long long s = 0; s < last - first && rc == RK_JPEG_OK; ++s) rc = segs[(long long)j * max_segments + s];
+        }
+    }
+    status[j] = rc;
 }
 
 __global__ __launch_bounds__(kBlock) void k_jpeg_idct(const rk_jpeg_frame* __restrict__ frames,
@@ -196,6 +336,71 @@ int rk_jpeg_decode_u8(const unsigned char* streams, long long stream_bytes, cons
     hipLaunchKernelGGL(k_jpeg_idct, dim3(n, kIdctSlices), dim3(kBlock), 0, s, frames, qtabs, ws, status);
     hipLaunchKernelGGL(k_jpeg_colour, dim3(n, kColourSlices), dim3(kBlock), 0, s, frames, ws, status, rgb, rgb_bytes);
     hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, n);
+    return launch_status();
+}
+
+int rk_jpeg_build_index(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                        const rk_jpeg_huff* htabs, int nq, int nh, int n, const int* seg_mcus, const long long* entry_off,
+                        rk_jpeg_entry* entries, long long n_entries, int* status, rk_stream_t stream) {
+    using namespace rk;
+    if (!streams || !frames || !htabs || !seg_mcus || !entry_off || !entries || !status) return RK_ERR_NULL_POINTER;
+    if (n < 1 || n > 65535 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || stream_bytes < 0 || n_entries < 0)
+        return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)status & 3) || ((uintptr_t)seg_mcus & 3) ||
+        ((uintptr_t)entry_off & 7) || ((uintptr_t)entries & 7))
+        return RK_ERR_BAD_DIMS;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_jpeg_index, dim3(n), dim3(kWave), 0, s, streams, stream_bytes, frames, htabs, nq, nh, seg_mcus,
+                       entry_off, entries, n_entries, status);
+    hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, n);
+    return launch_status();
+}
+
+size_t rk_jpeg_indexed_workspace_bytes(const rk_jpeg_frame* frames_host, int n, const int* pick_host, int m, int max_segments) {
+    if (!frames_host || !pick_host || n < 1 || m < 1 || max_segments < 1) return 0;
+    long long total = rkjpeg::indexed_head_bytes(m, max_segments) + rkjpeg::offset_table_bytes(m);
+    for (int j = 0; j < m; ++j)
+        if (pick_host[j] >= 0 && pick_host[j] < n) total += rkjpeg::frame_workspace_bytes(frames_host[pick_host[j]]);
+    return (size_t)total;
+}
+
+int rk_jpeg_decode_indexed_u8(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                              const unsigned short* qtabs, const rk_jpeg_huff* htabs, int nq, int nh, int n,
+                              const rk_jpeg_entry* entries, long long n_entries, const long long* entry_off,
+                              const int* seg_mcus, const int* build_status, const int* pick, const long long* rgb_off, int m,
+                              int max_segments, unsigned char* rgb, long long rgb_bytes, void* workspace,
+                              size_t workspace_bytes, int* status, rk_stream_t stream) {
+    using namespace rk;
+    if (!streams || !frames || !qtabs || !htabs || !entries || !entry_off || !seg_mcus || !build_status || !pick || !rgb_off ||
+        !rgb || !status)
+        return RK_ERR_NULL_POINTER;
+    if (n < 1 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || m < 1 || m > 65535 || max_segments < 1 || max_segments > 65535 ||
+        stream_bytes < 0 || rgb_bytes < 0 || n_entries < 0)
+        return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)qtabs & 1) || ((uintptr_t)status & 3) ||
+        ((uintptr_t)entries & 7) || ((uintptr_t)entry_off & 7) || ((uintptr_t)seg_mcus & 3) || ((uintptr_t)build_status & 3) ||
+        ((uintptr_t)pick & 3) || ((uintptr_t)rgb_off & 7))
+        return RK_ERR_BAD_DIMS;
+    const long long head = rkjpeg::indexed_head_bytes(m, max_segments);
+    if (!workspace || ((uintptr_t)workspace & 15) || (long long)workspace_bytes < head + rkjpeg::offset_table_bytes(m))
+        return RK_ERR_WORKSPACE;
+    const hipStream_t s = (hipStream_t)stream;
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    rk_jpeg_frame* gathered = reinterpret_cast<rk_jpeg_frame*>(base);
+    int* segs = reinterpret_cast<int*>(base + rkjpeg::gathered_bytes(m));
+    unsigned char* ws = base + head;                    // the plain decode's workspace: offset table, frame regions
+    const long long ws_bytes = (long long)workspace_bytes - head;
+    const int groups = (m + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_jpeg_gather, dim3(groups), dim3(kBlock), 0, s, frames, n, pick, rgb_off, m, gathered);
+    hipLaunchKernelGGL(k_jpeg_plan, dim3(1), dim3(kBlock), 0, s, gathered, m, stream_bytes, rgb_bytes, nq, nh,
+                       reinterpret_cast<long long*>(ws), ws_bytes, status);
+    hipLaunchKernelGGL(k_jpeg_entropy_seg, dim3(m, max_segments), dim3(kWave), 0, s, streams, gathered, htabs, entries, n_entries,
+                       entry_off, seg_mcus, build_status, pick, ws, status, segs);
+    hipLaunchKernelGGL(k_jpeg_seg_status, dim3(groups), dim3(kBlock), 0, s, gathered, n_entries, entry_off, seg_mcus, build_status,
+                       pick, segs, m, max_segments, status);
+    hipLaunchKernelGGL(k_jpeg_idct, dim3(m, kIdctSlices), dim3(kBlock), 0, s, gathered, qtabs, ws, status);
+    hipLaunchKernelGGL(k_jpeg_colour, dim3(m, kColourSlices), dim3(kBlock), 0, s, gathered, ws, status, rgb, rgb_bytes);
+    hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, m);
     return launch_status();
 }
 

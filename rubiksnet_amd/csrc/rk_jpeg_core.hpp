@@ -1,7 +1,8 @@
 // rk_jpeg_core.hpp -- the baseline JPEG decode core of rk_jpeg.hip as plain host/device C++: record check and
-// geometry, bit reader, Huffman step, one scan's entropy decode, jidctint's ISLOW IDCT, fancy upsampling and
-// YCbCr -> RGB.  The kernels only distribute this code over lanes; tests/jpeg_core_main.cpp compiles the same text for
-// the CPU under AddressSanitizer / UBSan, which is the bounds proof for the kernels' logic.
+// geometry, bit reader, Huffman step, one scan's entropy decode -- whole, or a span of MCUs resumed at a recorded entry,
+// and the walk that records those entries -- jidctint's ISLOW IDCT, fancy upsampling and YCbCr -> RGB.  The kernels only
+// distribute this code over lanes; tests/jpeg_core_main.cpp and tests/jpeg_index_main.cpp compile the same text for the
+// CPU under AddressSanitizer / UBSan, which is the bounds proof for the kernels' logic.
 //
 // Every function is bounded by counts from the record and reads the stream through a source object that the caller
 // bounds; arithmetic that a hostile stream could overflow is done in unsigned (two's complement wrap, as the hardware).
@@ -99,20 +100,63 @@ RKJ_HD int check_record(const rk_jpeg_frame& f, long long stream_bytes, long lon
     return RK_JPEG_OK;
 }
 
+// A resident record (rk_jpeg_build_index): check_record without the output range and the workspace, which a resident
+// frame gets only when it is picked.
+RKJ_HD int check_resident(const rk_jpeg_frame& f, long long stream_bytes, int nq, int nh) {
+    Geometry g;
+    if (!geometry(f, g)) return RK_JPEG_BAD_RECORD;
+    if (f.stream_off < 0 || f.stream_len < 0 || f.stream_off > stream_bytes || f.stream_len > stream_bytes - f.stream_off)
+        return RK_JPEG_BAD_RECORD;
+    if (f.restart_interval < 0 || f.restart_interval > 65535) return RK_JPEG_BAD_RECORD;
+    for (int c = 0; c < g.ncomp; ++c)
+        if (f.quant[c] >= nq || f.dc[c] >= nh || f.ac[c] >= nh) return RK_JPEG_BAD_RECORD;
+    return RK_JPEG_OK;
+}
+
+// Bytes in front of the plain workspace in an indexed decode: the m gathered records, then the per-segment codes.
+RKJ_HD long long gathered_bytes(int m) { return (long long)m * 64; }
+RKJ_HD long long indexed_head_bytes(int m, int max_segments) {
+    return gathered_bytes(m) + ((((long long)m * max_segments) * 4 + 15) & ~15LL);
+}
+
 // ------------------------------------------------------------------------------------------------ bits
 // Src: `int byte(long long pos)` for 0 <= pos < len, the byte at that position of the frame's segment.
 // The reader never asks for a position outside [0, len).  Bits past the end or past a marker read as zero and are
 // counted (`fake`): a decoder that used one has run off the data.
-template <class Src>
+// kTrack: keep what bit_pos() needs; the whole-frame decode never asks and does without.
+template <class Src, bool kTrack = true>
 struct BitReader {
     Src& src;
     long long pos, len;
     unsigned acc;           // the next bits, most significant first
     int bits;               // valid bits in acc
     int fake;               // how many of them are zeros that stand for missing data
+    unsigned wide;          // a 4-bit shift register, newest in bit 0: was the data byte read k bytes ago an FF 00 pair?
     bool stopped;           // a marker or the end was reached: nothing more is read
 
-    RKJ_HD BitReader(Src& s, long long n) : src(s), pos(0), len(n), acc(0), bits(0), fake(0), stopped(false) {}
+    RKJ_HD BitReader(Src& s, long long n) : src(s), pos(0), len(n), acc(0), bits(0), fake(0), wide(0), stopped(false) {}
+
+    // Start afresh at raw bit position p (0 <= p <= 8 * len; see bit_pos).  A position inside the 00 of an FF 00 pair, or
+    // any other a walk never stood at, is read as what the bytes from there on spell: bounded like everything else.
+    RKJ_HD void seek(long long p) {
+        pos = p >> 3;
+        acc = 0;
+        bits = fake = 0;
+        wide = 0;
+        stopped = false;
+        fill();
+        drop((int)(p & 7));
+    }
+    // 8 * (offset of the raw byte that holds the next unread bit) + (bit in that byte, 0 = most significant); FF 00 is two
+    // raw bytes and its bits live in the FF.  With no real bit left: the byte the reader would read next (the marker's FF
+    // or len once stopped), bit 0.  The reader holds at most four data bytes, whose raw widths `wide` remembers.
+    RKJ_HD long long bit_pos() const {
+        const int real = bits - fake;
+        if (real <= 0) return pos * 8;
+        const int nb = (real + 7) >> 3;                                     // 1..4 data bytes held, the first in part
+        const int raw = nb + __builtin_popcount(wide & ((1u << nb) - 1u));
+        return (pos - raw) * 8 + (nb * 8 - real);
+    }
 
     RKJ_HD bool at_stop() {
         if (pos >= len) return true;
@@ -129,8 +173,10 @@ struct BitReader {
                     b = (unsigned)src.byte(pos) & 0xFFu;
                     if (b != 0xFF) {
                         pos += 1;
+                        if (kTrack) wide <<= 1;
                     } else if (pos + 1 < len && src.byte(pos + 1) == 0x00) {
                         pos += 2;                       // FF 00 is the data byte FF
+                        if (kTrack) wide = (wide << 1) | 1u;
                     } else {
                         stopped = true;                 // a marker (or a lone FF at the end): not consumed
                         b = 0;
@@ -174,8 +220,8 @@ struct BitReader {
 };
 
 // One Huffman symbol, or -1 when the bits are no code.  Every index is masked: the table is untrusted device data.
-template <class Src>
-RKJ_HD int huff_symbol(BitReader<Src>& br, const rk_jpeg_huff& h) {
+template <class Src, bool kTrack>
+RKJ_HD int huff_symbol(BitReader<Src, kTrack>& br, const rk_jpeg_huff& h) {
     br.fill();
     const unsigned e = h.look[br.peek(9) & 511];
     const int l = (int)(e >> 8);
@@ -194,8 +240,8 @@ RKJ_HD int huff_symbol(BitReader<Src>& br, const rk_jpeg_huff& h) {
 }
 
 // s bits as a JPEG signed magnitude (1 <= s <= 15)
-template <class Src>
-RKJ_HD int receive_extend(BitReader<Src>& br, int s) {
+template <class Src, bool kTrack>
+RKJ_HD int receive_extend(BitReader<Src, kTrack>& br, int s) {
     br.fill();
     const int v = (int)br.peek(s);
     br.drop(s);
@@ -208,15 +254,53 @@ RKJ_HD int receive_extend(BitReader<Src>& br, int s) {
 // memory round trip on the device), end_block(block_index) after each; the blocks come in scan order (MCU by MCU; in an MCU the luma blocks row by row, then Cb, then Cr).
 // tabs: the frame's six tables, DC of component c at [c], AC at [3 + c].
 // Returns a RK_JPEG_* code; on an error the blocks from the failing one on have not been written.
-template <class Src, class Sink>
-RKJ_HD int decode_scan(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, Sink& sink) {
-    BitReader<Src> br(src, f.stream_len);
+//
+// The walk can be entered at any MCU m whose ENTRY is known: the reader's bit_pos() and the three DC predictors at the
+// top of the loop's iteration m, before that iteration's restart handling (rk_jpeg_entry, include/rubiks_hip.h).  The
+// restart state needs no storing: with R = restart_interval > 0, the iterations R, 2R, ... <= m - 1 have each passed a
+// marker, j = (m - 1) / R of them, so the next marker is RST(j & 7), and the countdown was set to R at iteration j * R (or
+// at the start) and has run m - j * R times since.
+struct NoRecorder {
+    static constexpr bool enabled = false;
+    RKJ_HD void at(long long, long long, int, int, int) {}
+};
+
+RKJ_HD bool entry_equals(const rk_jpeg_entry& e, long long bit_pos, int p0, int p1, int p2) {
+    return e.bit_pos == bit_pos && e.pred[0] == p0 && e.pred[1] == p1 && e.pred[2] == p2;
+}
+
+// MCUs [m_begin, m_end) of the scan, resumed at `entry`; block indices handed to the sink stay frame-global.  A span that
+// ends before the last MCU must leave the reader exactly at *next (position and predictors), the last one at the end of
+// the stream (BitReader::finish): spans that each return RK_JPEG_OK therefore tile the stream.  The entries are
+// untrusted: RK_JPEG_BAD_INDEX, before any read, for a range outside the frame, a bit_pos outside [0, 8 * stream_len], a
+// predictor outside +-2047 or an entry of MCU 0 that is not zero; RK_JPEG_BAD_INDEX after the span's last MCU where
+// the reader does not stand at *next.  rec.at(m, bit_pos, pred0, pred1, pred2) sees every entry of the span when
+// Rec::enabled.  kWhole: the caller only ever walks [0, nmcu) from the zero entry (anything else is RK_JPEG_BAD_INDEX), so
+// no position is asked for unless a recorder does, and the reader keeps none: the plain decode's loop as it always was.
+template <bool kWhole, class Src, class Sink, class Rec>
+RKJ_HD int walk_span(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, Sink& sink, Rec& rec,
+                     const rk_jpeg_entry& entry, long long m_begin, long long m_end, const rk_jpeg_entry* next) {
     const int nluma = g.ncomp == 1 ? 1 : g.hs * g.vs;
     const long long nmcu = (long long)g.mcux * g.mcuy;
-    int pred0 = 0, pred1 = 0, pred2 = 0;                    // scalars, not an array: a lane-private array indexed by c lives in scratch memory
+    if (m_begin < 0 || m_begin >= m_end || m_end > nmcu || (m_end < nmcu && !next)) return RK_JPEG_BAD_INDEX;
+    if (kWhole && (m_begin != 0 || m_end != nmcu)) return RK_JPEG_BAD_INDEX;
+    if (entry.bit_pos < 0 || entry.bit_pos > f.stream_len * 8) return RK_JPEG_BAD_INDEX;
+    int pred0 = entry.pred[0], pred1 = entry.pred[1], pred2 = entry.pred[2];    // scalars, not an array: a lane-private array indexed by c lives in scratch memory
+    if (pred0 < -2047 || pred0 > 2047 || pred1 < -2047 || pred1 > 2047 || pred2 < -2047 || pred2 > 2047) return RK_JPEG_BAD_INDEX;
+    if (m_begin == 0 && (entry.bit_pos | pred0 | pred1 | pred2) != 0) return RK_JPEG_BAD_INDEX;
+    BitReader<Src, !kWhole || Rec::enabled> br(src, f.stream_len);
     int next_rst = 0, until_rst = f.restart_interval;
-    long long block = 0;
-    for (long long m = 0; m < nmcu; ++m) {
+    if (!kWhole && m_begin > 0) {
+        br.seek(entry.bit_pos);
+        if (f.restart_interval > 0) {
+            const long long j = (m_begin - 1) / f.restart_interval;
+            next_rst = (int)(j & 7);
+            until_rst = (int)(f.restart_interval - (m_begin - j * f.restart_interval));
+        }
+    }
+    long long block = m_begin * g.bpm;
+    for (long long m = m_begin; m < m_end; ++m) {
+        if (Rec::enabled) rec.at(m, br.bit_pos(), pred0, pred1, pred2);
         if (f.restart_interval > 0) {
             if (until_rst == 0) {
                 const int rc = br.restart(next_rst);
@@ -261,7 +345,69 @@ RKJ_HD int decode_scan(const rk_jpeg_frame& f, const Geometry& g, Src& src, cons
             sink.end_block(block);
         }
     }
-    return br.finish();
+    if (kWhole || m_end == nmcu) return br.finish();
+    return entry_equals(*next, br.bit_pos(), pred0, pred1, pred2) ? RK_JPEG_OK : RK_JPEG_BAD_INDEX;
+}
+
+// The whole frame: the span [0, nmcu) from the zero entry.
+template <class Src, class Sink>
+RKJ_HD int decode_scan(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, Sink& sink) {
+    rk_jpeg_entry zero = {0, {0, 0, 0}, 0};
+    NoRecorder none;
+    return walk_span<true>(f, g, src, tabs, sink, none, zero, 0, (long long)g.mcux * g.mcuy, nullptr);
+}
+
+template <class Src, class Sink>
+RKJ_HD int decode_span(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, Sink& sink,
+                       const rk_jpeg_entry& entry, long long m_begin, long long m_end, const rk_jpeg_entry* next) {
+    NoRecorder none;
+    return walk_span<false>(f, g, src, tabs, sink, none, entry, m_begin, m_end, next);
+}
+
+// ------------------------------------------------------------------------------------------------ the scan index
+// Segments of a frame walked in pieces of E MCUs: how many, and is the frame's row of the index table usable?
+RKJ_HD long long segment_count(const Geometry& g, int E) { return ((long long)g.mcux * g.mcuy + E - 1) / E; }
+RKJ_HD bool index_row_ok(const Geometry& g, int E, long long first, long long last, long long n_entries) {
+    if (E < 1 || first < 0 || last < first || last > n_entries) return false;
+    return last - first == segment_count(g, E);
+}
+
+struct NullSink {
+    RKJ_HD void put(int, int) {}
+    RKJ_HD void end_block(long long) {}
+};
+
+// Writes the entry of every E-th MCU; `writer` says whether this caller stores (one lane of a wave that walks together).
+struct EntryRecorder {
+    static constexpr bool enabled = true;
+    rk_jpeg_entry* out;
+    int E, left;            // left: MCUs until the next entry
+    bool writer;
+    RKJ_HD void at(long long, long long bit_pos, int p0, int p1, int p2) {
+        if (left == 0) {
+            if (writer) {
+                out->bit_pos = bit_pos;
+                out->pred[0] = (short)p0;
+                out->pred[1] = (short)p1;
+                out->pred[2] = (short)p2;
+                out->reserved = 0;
+            }
+            ++out;
+            left = E;
+        }
+        --left;
+    }
+};
+
+// The one sequential walk a resident frame gets: no coefficient is stored, out[s] becomes the entry of MCU s * E for
+// every segment s (the caller has checked index_row_ok).  Returns the code decode_scan returns for the frame.
+template <class Src>
+RKJ_HD int record_index(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, int E,
+                        rk_jpeg_entry* out, bool writer) {
+    rk_jpeg_entry zero = {0, {0, 0, 0}, 0};
+    NullSink sink;
+    EntryRecorder rec{out, E, 0, writer};
+    return walk_span<true>(f, g, src, tabs, sink, rec, zero, 0, (long long)g.mcux * g.mcuy, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ IDCT

@@ -249,6 +249,12 @@ class RubiksDataset(_Sampled):
         images = [self._load_image(record.path, p)[0] for p in range(1, record.num_frames + 1)]
         return torch.from_numpy(np.stack([np.asarray(im, dtype=np.uint8) for im in images])), record.label
 
+    def whole_bytes(self, index):
+        """whole() for the device decoder: every frame of a video as _load_bytes gives it (the file's bytes, or uint8
+        [H, W, 3] where the host had to decode it, with the same stand-in rule), and its label."""
+        record = self.video_list[index]
+        return [self._load_bytes(record.path, p) for p in range(1, record.num_frames + 1)], record.label
+
 
 class InMemoryVideos(_Sampled):
     """RubiksDataset's sampling over videos that are already decoded: `videos` a list of uint8 [F, H, W, 3] tensors (of
@@ -587,10 +593,29 @@ class DeviceFrameCache(_Feeder):
 
     source: a RubiksDataset or InMemoryVideos (its sampling flags are used), or a list of (uint8 [F, H, W, 3], label) with
     the sampling given by `num_segments` and the other keywords.  budget_bytes: the most HBM the arena may take; a set
-    that needs more raises.  Iteration, output shapes and row order are FrameLoader's; work runs on the caller's stream."""
+    that needs more raises.  Iteration, output shapes and row order are FrameLoader's; work runs on the caller's stream.
+
+    resident="jpeg" (with a RubiksDataset(..., decode="device")) keeps the FILES' bytes in HBM instead of the decoded
+    frames, about a sixth of the bytes for ordinary video frames: the files are read and parsed on the host once, their
+    entropy-coded segments, tables and a scan index (jpeg.pack_resident; one entry per MCU row) go to the device, and
+    rk_jpeg_build_index walks every scan there once.  Per batch the sampling and the boxes are drawn exactly as for "rgb"
+    (the same generator calls in the same order), jpeg.pick_tables names the frames the batch reads, one
+    rk_jpeg_decode_indexed_u8 launch decodes them -- a chain per MCU row -- into the batch's RGB arena, and the unchanged
+    ragged launch follows: with equal seeds clips and labels are bit-identical to "rgb".  budget_bytes counts the blob, the
+    entries, the host-decoded frames and one batch's RGB arena and workspace (grown on demand).  Files jpeg.parse_jpeg
+    refuses are decoded once with Pillow, stay resident as RGB and are copied into place per batch (`fallback_frames`
+    counts them); frames the index build refused come out as zero frames, `decode_errors()` reads how many such frames
+    went out so far.  A batch stays valid until the next one is asked for."""
 
     def __init__(self, source, batch, split, device="cuda:0", dtype=torch.float32, size=224, views=1, box_fn=None, seed=0,
-                 temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5, budget_bytes=4 << 30, **sampling):
+                 temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5, budget_bytes=4 << 30, resident="rgb",
+                 **sampling):
+        if resident not in ("rgb", "jpeg"):
+            raise ValueError("resident must be 'rgb' or 'jpeg', got %r" % (resident,))
+        if resident == "jpeg" and not (isinstance(source, RubiksDataset) and source.decode == "device"):
+            raise ValueError("resident='jpeg' keeps the files' bytes: it needs a RubiksDataset(..., decode='device'), not "
+                             "%s" % ("in-memory videos, which are decoded already" if not isinstance(source, RubiksDataset)
+                                     else "a decode='host' dataset"))
         if not isinstance(source, _Sampled):
             videos, labels = zip(*source) if len(source) else ((), ())
             sampling.setdefault("random_shift", split == "train")
@@ -603,6 +628,10 @@ class DeviceFrameCache(_Feeder):
         self._init_feeder(source, batch, split, device, dtype, size, views, box_fn, temporal_clips, seed, flip_p)
         self.source, self.drop_last = source, drop_last
         self.shuffle = (split == "train") if shuffle is None else shuffle
+        self.resident, self.budget_bytes, self.fallback_frames = resident, int(budget_bytes), 0
+        if resident == "jpeg":
+            self._init_jpeg()
+            return
         need, whole = 0, []
         for i in range(len(source)):            # the budget is checked as the videos come, before the device sees a byte
             whole.append(source.whole(i))
@@ -616,6 +645,78 @@ class DeviceFrameCache(_Feeder):
         self._dev_labels = self.labels.to(self.device)
         _mean_std_on(self.device, IMAGENET_MEAN, IMAGENET_STD)
 
+    def _init_jpeg(self):
+        source = self.source
+        self.packed = jpeg.pack_resident([source.whole_bytes(i) for i in range(len(source))])
+        res = self.packed
+        self.labels, self.fallback_frames = res.labels, len(res.fallback)
+        self.records = torch.cat([torch.zeros(len(res.videos), 1, dtype=torch.int64), res.videos[:, [2, 3, 1]]], dim=1)
+        sizes = [f.numel() for f in res.fallback]
+        self._fallback_off = [0] + np.cumsum(sizes).tolist()
+        n_entries = int(res.entry_off[-1])
+        tables = res.seg_mcus.numel() * 4 + res.entry_off.numel() * 8 + (int(res.layout[0]) + 1) * 4
+        self._fixed_bytes = res.blob.numel() + max(n_entries, 1) * 16 + tables + sum(sizes)
+        if self._fixed_bytes > self.budget_bytes:
+            raise RuntimeError("DeviceFrameCache: the %d videos take %d bytes as files, over the budget of %d bytes; raise "
+                               "budget_bytes or stream with FrameLoader" % (len(source), self._fixed_bytes, self.budget_bytes))
+        self.index = jpeg.build_index(res, self.device)
+        self._fallback = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
+        for frame, at in zip(res.fallback, self._fallback_off):
+            self._fallback[at:at + frame.numel()].copy_(frame.reshape(-1))
+        (frames, _, _, _), _ = jpeg.sections(res.blob, res.layout)
+        self._host_frames = np.frombuffer(frames.numpy().tobytes(), dtype=jpeg.FRAME_DTYPE)
+        self._frame_ws = jpeg.frame_workspace_bytes(self._host_frames)
+        self._rgb = self._ws = self._status = None
+        self._errors = torch.zeros((), dtype=torch.int64, device=self.device)
+        self._dev_labels = self.labels.to(self.device)
+        _mean_std_on(self.device, IMAGENET_MEAN, IMAGENET_STD)
+
+    @property
+    def resident_bytes(self):
+        """Bytes of HBM the cache holds now: the arena ("rgb"), or the blob, the index, the host-decoded frames and the
+        batch buffers as far as they have grown ("jpeg")."""
+        if self.resident == "rgb":
+            return self.arena.numel()
+        return self._fixed_bytes + sum(t.numel() * t.element_size() for t in (self._rgb, self._ws, self._status) if t is not None)
+
+    def decode_errors(self):
+        """Frames that went out as zero frames so far because the device refused them (resident="jpeg"; 0 otherwise).
+        Waits for the device: ask once, at the end of an epoch."""
+        return int(self._errors.item()) if self.resident == "jpeg" else 0
+
+    def _grown(self, t, need, make):
+        """FrameLoader._grown under the budget: the batch buffers grow on demand, and count."""
+        if t is not None and t.numel() >= need:
+            return t
+        new = make(need + need // 4)
+        have = self.resident_bytes - (t.numel() * t.element_size() if t is not None else 0)
+        if have + new.numel() * new.element_size() > self.budget_bytes:
+            raise RuntimeError("DeviceFrameCache: a batch needs a buffer of %d bytes beside the %d resident, over the budget "
+                               "of %d bytes" % (new.numel() * new.element_size(), have, self.budget_bytes))
+        return new
+
+    def _decode_batch(self, ids, numbers):
+        """resident="jpeg": the frames `numbers` (0-based, per video of `ids`) decoded into the batch's RGB arena ->
+        (arena, clips rows for it, per-video frame numbers remapped into it)."""
+        t = jpeg.pick_tables(self.packed, ids.tolist(), numbers)
+        m = t.pick.numel()
+        self._rgb = self._grown(self._rgb, t.rgb_bytes, lambda k: torch.empty(k, dtype=torch.uint8, device=self.device))
+        rgb = self._rgb[:t.rgb_bytes]
+        if m:
+            need = jpeg.indexed_workspace_bytes_for(self._host_frames, t.pick.numpy(), t.max_segments, self._frame_ws)
+            self._ws = self._grown(self._ws, need, lambda k: torch.empty(k, dtype=torch.uint8, device=self.device))
+            self._status = self._grown(self._status, m + 1, lambda k: torch.zeros(k, dtype=torch.int32, device=self.device))
+            with _near_gpu(self.device):
+                pick, rgb_off = t.pick.pin_memory(), t.rgb_off.pin_memory()
+            status = self._status[:m + 1]
+            jpeg.launch_decode_indexed(self.index, pick.to(self.device, non_blocking=True),
+                                       rgb_off.to(self.device, non_blocking=True), t.max_segments, rgb, self._ws, status)
+            self._errors += status[m]
+        for f, off in t.fallback:
+            at, k = self._fallback_off[f], self._fallback_off[f + 1] - self._fallback_off[f]
+            rgb[off:off + k].copy_(self._fallback[at:at + k])
+        return rgb, t.clips, t.frame_idx
+
     def __len__(self):
         n = len(self.source)
         return n // self.batch if self.drop_last else (n + self.batch - 1) // self.batch
@@ -626,6 +727,21 @@ class DeviceFrameCache(_Feeder):
         for b in range(len(self)):
             ids = order[b * self.batch:(b + 1) * self.batch]
             clips = self.records[ids]
+            if self.resident == "jpeg":
+                numbers = [(torch.tensor(self.source.frame_numbers(nf, self._gen), dtype=torch.int64).clamp_(1, nf) - 1).tolist()
+                           for nf in clips[:, 3].tolist()]
+                boxes = self._boxes([(int(h), int(w)) for h, w in clips[:, 1:3].tolist()])
+                arena, clips, local = self._decode_batch(ids, numbers)
+                rows = []
+                for p in local:
+                    p = torch.from_numpy(p).to(torch.int32)
+                    T = p.numel() // self.temporal_clips
+                    rows.append(p[_temporal_index(p.numel(), self.temporal_clips, self.crops).long()].view(-1, T))
+                frame_idx = torch.cat(rows)
+                out = augment.ragged_u8_to_clips(arena, clips, frame_idx, boxes, self.size, views=self.views, dtype=self.dtype)
+                self.tables = {"videos": ids, "clips": clips, "frame_idx": frame_idx, "boxes": boxes, "labels": self.labels[ids]}
+                yield out, self._dev_labels[ids.to(self.device)]
+                continue
             rows = []
             for _, _, _, nf in clips.tolist():
                 p = torch.tensor(self.source.frame_numbers(nf, self._gen), dtype=torch.int32).clamp_(1, nf) - 1

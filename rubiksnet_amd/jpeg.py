@@ -12,6 +12,14 @@ A DataLoader worker only reads the files and walks their headers; the file bytes
   launch_decode       the launch on device tensors
   decode_jpeg_frames  upload + launch for one packed batch
 
+A set that stays on the device keeps its files' bytes there and is decoded by scan index (rk_jpeg_build_index,
+rk_jpeg_decode_indexed_u8; dataset.DeviceFrameCache(resident="jpeg")):
+
+  pack_resident          a whole set as one blob + the index tables (one segment per MCU row by default)
+  build_index            upload + the one sequential walk every frame gets
+  pick_tables            per batch, on the host: which resident frames go where in the batch's RGB arena
+  launch_decode_indexed  the launch on device tensors
+
 There is no CPU path: a missing library is an error (tests compare with Pillow).
 """
 import collections
@@ -21,10 +29,13 @@ import numpy as np
 import torch
 
 __all__ = ["JpegHeader", "parse_jpeg", "pack_jpeg_clips", "PackedJpeg", "decode_jpeg_frames", "launch_decode",
-           "workspace_bytes_for", "huffman_record", "FRAME_DTYPE", "HUFF_DTYPE", "STATUS_NAMES", "MAX_SIDE"]
+           "workspace_bytes_for", "huffman_record", "FRAME_DTYPE", "HUFF_DTYPE", "STATUS_NAMES", "MAX_SIDE", "ENTRY_DTYPE",
+           "ResidentJpeg", "pack_resident", "DeviceIndex", "build_index", "PickTables", "pick_tables",
+           "frame_workspace_bytes", "indexed_workspace_bytes_for", "launch_decode_indexed"]
 
 MAX_SIDE = 16384
-STATUS_NAMES = ("ok", "bad record", "bad code", "run past 63", "truncated", "bad restart", "trailing data", "bad value")
+STATUS_NAMES = ("ok", "bad record", "bad code", "run past 63", "truncated", "bad restart", "trailing data", "bad value",
+                "bad index")
 
 # include/rubiks_hip.h: rk_jpeg_frame (64 bytes) and rk_jpeg_huff (1424 bytes)
 FRAME_DTYPE = np.dtype({"names": ["stream_off", "stream_len", "rgb_off", "width", "height", "components", "sampling",
@@ -345,6 +356,182 @@ def launch_decode(streams, frames, qtabs, htabs, n, rgb, workspace, status, nq=N
     _native.launch("rk_jpeg_decode_u8", rgb.device, streams.data_ptr(), streams.numel(), frames.data_ptr(), qtabs.data_ptr(),
                    htabs.data_ptr(), nq, nh, n, rgb.data_ptr(), rgb.numel(), workspace.data_ptr(), workspace.numel(),
                    status.data_ptr())
+
+
+# ------------------------------------------------------------------------------------------------- resident sets
+ENTRY_DTYPE = np.dtype([("bit_pos", "<i8"), ("pred", "<i2", 3), ("reserved", "<i2")])      # rk_jpeg_entry
+assert ENTRY_DTYPE.itemsize == 16
+MAX_LAUNCH = 65535                                          # frames per build call, picks per decode call
+
+ResidentJpeg = collections.namedtuple("ResidentJpeg", [
+    "blob",             # uint8: the records of every device-decoded frame, tables, streams -- PackedJpeg's blob and layout
+    "layout",
+    "seg_mcus",         # int32 [n]: E of each record (default: its MCUs per row)
+    "entry_off",        # int64 [n + 1]: exclusive sum of the records' segment counts ceil(nmcu / E)
+    "segments",         # int64 [n]: those counts
+    "videos",           # int64 [V, 4]: first slot, frame count, H, W; frame k of video v is slot videos[v, 0] + k
+    "slots",            # int64 [slots]: the slot's record, or -1 - f for the f-th host-decoded frame
+    "fallback",         # [uint8 [H, W, 3]]: the frames parse_jpeg refused, decoded here with Pillow
+    "labels",           # int64 [V]
+])
+
+
+def _mcus(width, height, components, sampling):
+    hs, vs = (2 if components == 3 and sampling >= 1 else 1), (2 if components == 3 and sampling == 2 else 1)
+    return (width + 8 * hs - 1) // (8 * hs), (height + 8 * vs - 1) // (8 * vs)
+
+
+def pack_resident(videos, seg_mcus=None):
+    """A set of videos for rk_jpeg_build_index / rk_jpeg_decode_indexed_u8.  videos: [(frames, label)] as pack_jpeg_clips
+    takes them (a frame: the bytes of its file, or uint8 [H, W, 3]); all frames of a video share one size (ValueError
+    otherwise).  seg_mcus: MCUs per segment -- None: one MCU row; an int: that for every frame; or one per device-decoded
+    frame.  Returns a ResidentJpeg: pack_jpeg_clips' blob (records, de-duplicated tables, streams; rgb_off is 0, a
+    resident frame gets its place when it is picked) and the index tables.  Files parse_jpeg refuses are decoded here,
+    once, and stay RGB."""
+    packed = pack_jpeg_clips(videos)
+    (frames, _, _, _), (n, _, _) = sections(packed.blob, packed.layout)
+    rec = np.frombuffer(frames.numpy(), dtype=FRAME_DTYPE)                  # a view: the edits land in the blob
+    host = {int(off): i for i, (off, _) in enumerate(packed.fallback)}
+    rows, slots, r = [], [], 0
+    for off, h, w, k in packed.clips.tolist():
+        rows.append((len(slots), k, h, w))
+        for j in range(k):
+            at = off + j * h * w * 3
+            if at in host:
+                slots.append(-1 - host[at])
+            else:
+                slots.append(r)
+                r += 1
+    assert r == n
+    rec["rgb_off"][:] = 0
+    mcux, mcuy = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for i, f in enumerate(rec):
+        mcux[i], mcuy[i] = _mcus(int(f["width"]), int(f["height"]), int(f["components"]), int(f["sampling"]))
+    E = mcux.copy() if seg_mcus is None else np.broadcast_to(np.asarray(seg_mcus, dtype=np.int64), (n,)).copy()
+    if n and (E.min() < 1 or E.max() >= 1 << 31):
+        raise ValueError("seg_mcus must be at least 1")
+    segments = (mcux * mcuy + E - 1) // E
+    entry_off = np.concatenate([[0], np.cumsum(segments)]).astype(np.int64)
+    return ResidentJpeg(packed.blob, packed.layout, torch.from_numpy(E.astype(np.int32)), torch.from_numpy(entry_off),
+                        torch.from_numpy(segments.astype(np.int64)), torch.tensor(rows, dtype=torch.int64).reshape(-1, 4),
+                        torch.tensor(slots, dtype=torch.int64), [frame for _, frame in packed.fallback], packed.labels)
+
+
+DeviceIndex = collections.namedtuple("DeviceIndex", [
+    "blob", "frames", "htabs", "qtabs", "streams", "n", "nh", "nq",      # the resident blob on the device and its sections
+    "seg_mcus", "entry_off", "entries", "n_entries",                     # int32 [n], int64 [n + 1], uint8 [n_entries * 16]
+    "status",                                                            # int32 [n + 1]: the build's codes, [n] their count
+])
+
+
+def build_index(resident, device="cuda:0"):
+    """Upload a ResidentJpeg and walk every scan once (rk_jpeg_build_index, in chunks of 65535 frames, current stream).
+    Returns a DeviceIndex; nothing waits for the device."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("build_index runs on a GPU (no CPU path)")
+    from . import _native
+    blob = resident.blob.to(device)
+    (frames, htabs, qtabs, streams), (n, nh, nq) = sections(blob, resident.layout)
+    n_entries = int(resident.entry_off[-1])
+    seg_mcus, entry_off = resident.seg_mcus.to(device), resident.entry_off.to(device)
+    entries = torch.zeros(max(n_entries, 1) * ENTRY_DTYPE.itemsize // 8, dtype=torch.int64, device=device).view(torch.uint8)
+    status = torch.zeros(n + 1, dtype=torch.int32, device=device)
+    for lo in range(0, n, MAX_LAUNCH):
+        k = min(MAX_LAUNCH, n - lo)
+        part = torch.zeros(k + 1, dtype=torch.int32, device=device)
+        _native.launch("rk_jpeg_build_index", device, streams.data_ptr(), streams.numel(),
+                       frames[lo * 64:].data_ptr(), htabs.data_ptr(), nq, nh, k, seg_mcus[lo:].data_ptr(),
+                       entry_off[lo:].data_ptr(), entries.data_ptr(), n_entries, part.data_ptr())
+        status[lo:lo + k].copy_(part[:k])
+        status[n] += part[k]
+    return DeviceIndex(blob, frames, htabs, qtabs, streams, n, nh, nq, seg_mcus, entry_off, entries, n_entries, status)
+
+
+PickTables = collections.namedtuple("PickTables", [
+    "pick",             # int32 [m]: the records to decode, each once
+    "rgb_off",          # int64 [m]: where each goes in the batch's RGB arena
+    "clips",            # int64 [B, 4]: the arena's rows for augment.ragged_u8_to_clips (offset, H, W, distinct frames)
+    "frame_idx",        # per video: int64 array, the given frame numbers remapped into that video's frames of the arena
+    "fallback",         # [(index in resident.fallback, offset in the arena)]
+    "rgb_bytes",
+    "max_segments",     # the largest segment count among the picked records (at least 1)
+])
+
+
+def pick_tables(resident, video_ids, frame_numbers_per_video):
+    """The tables of one batch, on the host.  video_ids: the batch's videos; frame_numbers_per_video: for each, the 0-based
+    frames its clips read.  A frame repeated inside a video's sample (short videos) is decoded once: the arena holds every
+    video's distinct frames in order of first use, back to back, and frame_idx says where each asked-for frame went."""
+    pick, rgb_off, rows, remapped, fallback, at, most = [], [], [], [], [], 0, 1
+    videos, slots, segments = resident.videos.numpy(), resident.slots.numpy(), resident.segments.numpy()   # views, no copies
+    for v, numbers in zip(video_ids, frame_numbers_per_video):
+        first, count, h, w = (int(x) for x in videos[int(v)])
+        place, local = {}, []
+        for p in (int(x) for x in numbers):
+            if not 0 <= p < count:
+                raise ValueError("frame %d of a video of %d frames" % (p, count))
+            if p not in place:
+                place[p] = len(place)
+                slot = int(slots[first + p])
+                off = at + place[p] * h * w * 3
+                if slot < 0:
+                    fallback.append((-1 - slot, off))
+                else:
+                    pick.append(slot)
+                    rgb_off.append(off)
+                    most = max(most, int(segments[slot]))
+            local.append(place[p])
+        rows.append((at, h, w, len(place)))
+        remapped.append(np.asarray(local, dtype=np.int64))
+        at += len(place) * h * w * 3
+    return PickTables(torch.tensor(pick, dtype=torch.int32), torch.tensor(rgb_off, dtype=torch.int64),
+                      torch.tensor(rows, dtype=torch.int64).reshape(-1, 4), remapped, fallback, at, most)
+
+
+def _head_bytes(m, max_segments):
+    return m * 64 + ((m * max_segments * 4 + 15) & ~15)
+
+
+def frame_workspace_bytes(frames):
+    """int64 per record of a FRAME_DTYPE array: the bytes of its region of the workspace (0 for sizes that are not valid),
+    what workspace_bytes_for sums, without a Python loop (a resident set asks once and indexes the answer per batch)."""
+    f = np.asarray(frames).reshape(-1)
+    w, h, nc, s = (f[k].astype(np.int64) for k in ("width", "height", "components", "sampling"))
+    ok = (w >= 1) & (w <= MAX_SIDE) & (h >= 1) & (h <= MAX_SIDE) & ((nc == 1) | ((nc == 3) & (s >= 0) & (s <= 2)))
+    hs, vs = np.where((nc == 3) & (s >= 1), 2, 1), np.where((nc == 3) & (s == 2), 2, 1)
+    blocks = ((w + 8 * hs - 1) // (8 * hs)) * ((h + 8 * vs - 1) // (8 * vs)) * np.where(nc == 1, 1, hs * vs + 2)
+    return np.where(ok, (blocks * 192 + 15) & ~15, 0)
+
+
+def indexed_workspace_bytes_for(frames, pick, max_segments, per_frame=None):
+    """rk_jpeg_indexed_workspace_bytes of a FRAME_DTYPE array and a pick list, in numpy.  per_frame: frame_workspace_bytes
+    of `frames`, where the caller keeps it."""
+    frames, pick = np.asarray(frames).reshape(-1), np.asarray(pick, dtype=np.int64).reshape(-1)
+    if frames.size < 1 or pick.size < 1 or max_segments < 1:
+        return 0
+    per_frame = frame_workspace_bytes(frames) if per_frame is None else per_frame
+    inside = pick[(pick >= 0) & (pick < frames.size)]
+    return _head_bytes(pick.size, int(max_segments)) + (((pick.size + 1) * 8 + 15) & ~15) + int(per_frame[inside].sum())
+
+
+def launch_decode_indexed(index, pick, rgb_off, max_segments, rgb, workspace, status):
+    """rk_jpeg_decode_indexed_u8 on the current stream.  index: a DeviceIndex; pick int32 [m], rgb_off int64 [m], rgb uint8
+    [rgb_bytes], workspace uint8 (16-byte aligned), status int32 [m + 1]: device tensors.  Nothing is allocated and the
+    host does not wait."""
+    from . import _native
+    m = pick.numel()
+    for name, t, dt in (("pick", pick, torch.int32), ("rgb_off", rgb_off, torch.int64), ("rgb", rgb, torch.uint8),
+                        ("workspace", workspace, torch.uint8), ("status", status, torch.int32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor on the GPU" % (name, dt))
+    if rgb_off.numel() != m or status.numel() < m + 1:
+        raise ValueError("pick [%d], rgb_off [%d], status [%d]: want m, m, m + 1" % (m, rgb_off.numel(), status.numel()))
+    _native.launch("rk_jpeg_decode_indexed_u8", rgb.device, index.streams.data_ptr(), index.streams.numel(),
+                   index.frames.data_ptr(), index.qtabs.data_ptr(), index.htabs.data_ptr(), index.nq, index.nh, index.n,
+                   index.entries.data_ptr(), index.n_entries, index.entry_off.data_ptr(), index.seg_mcus.data_ptr(),
+                   index.status.data_ptr(), pick.data_ptr(), rgb_off.data_ptr(), m, int(max_segments), rgb.data_ptr(),
+                   rgb.numel(), workspace.data_ptr(), workspace.numel(), status.data_ptr())
 
 
 def sections(blob, layout):
