@@ -812,6 +812,37 @@ typedef struct rk_jpeg_entry {
 int rk_jpeg_build_index(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
                         const rk_jpeg_huff* htabs, int nq, int nh, int n, const int* seg_mcus, const long long* entry_off,
                         rk_jpeg_entry* entries, long long n_entries, int* status, rk_stream_t stream);
+/* rk_jpeg_build_index_chunked: the same index -- status and entries identical to rk_jpeg_build_index's for the same
+ * arguments, frame by frame, good or corrupt -- without one frame-long chain per frame.  A frame without restart markers
+ * is cut into chunks of chunk_bytes raw bytes; a walk of a chunk takes a bit position to be the start of an MCU, decodes
+ * whole MCUs to the first MCU boundary at or past the chunk's end, and counts the MCUs and the DC differences.  Rounds in
+ * lock-step: first every chunk starts at its own first bit, then at the end the chunk before it reached in the round
+ * before (its own first bit again where that walk was refused).  Chunk 0 starts at bit 0, so after round r chunks
+ * 0 .. r - 1 hold the sequential walk; Huffman streams fall into step, so the fixed point -- which IS the sequential
+ * walk -- comes after a few rounds.  A final pass then walks every chunk from its true start, first MCU number and
+ * predictors and writes the entries; the frame has taken the chunked route only if that pass met no refusal, counted
+ * exactly nmcu MCUs and found the end of the stream as rk_jpeg_build_index's walk must find it.  Every other frame gets
+ * the sequential walk in the same call: restart_interval > 0, no fixed point within max_rounds, any refusal on the way,
+ * more than 4096 chunks (the largest chunk count that takes the chunked route), max_rounds == 0.
+ *   chunk_bytes  16, 32, 64, 128, 256 or 512        max_rounds  in [0, 64]
+ *   workspace    device, 16-byte aligned, rk_jpeg_chunked_workspace_bytes long (an offset table and 32 bytes per chunk);
+ *                a frame whose region does not fit takes the sequential walk
+ *   route        device int [n]: 0 where the sequential walk produced the frame's result, else the number of rounds
+ *                after which the chunked walk had converged
+ * One workgroup of 1024 lanes per frame, a lane per chunk (and per 1024th chunk after it); the frame's tables sit in
+ * LDS, the chunks' positions and sums in the workspace, the stream is read as aligned 8-byte words (the first and the
+ * last word of the arena byte by byte: nothing outside [streams, streams + stream_bytes) is read).  Four launches on `stream`, a linear chain: no allocation, no host wait, no atomics, no
+ * hand-off between workgroups; capturable.  Every loop is bounded: the rounds by max_rounds, a walk by its chunk's bits,
+ * an MCU by its blocks' 64 symbols each.  Returns as rk_jpeg_build_index, and RK_ERR_BAD_DIMS for a chunk_bytes or
+ * max_rounds outside the above, RK_ERR_WORKSPACE (NULL, not 16-byte aligned, shorter than the offset table).
+ * rk_jpeg_chunked_workspace_bytes: from a HOST copy of the records; 0 for a NULL table, n < 1 or a chunk_bytes outside
+ * the above.                                                                                                          */
+size_t rk_jpeg_chunked_workspace_bytes(const rk_jpeg_frame* frames_host, int n, int chunk_bytes);
+int rk_jpeg_build_index_chunked(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                                const rk_jpeg_huff* htabs, int nq, int nh, int n, const int* seg_mcus,
+                                const long long* entry_off, rk_jpeg_entry* entries, long long n_entries, int chunk_bytes,
+                                int max_rounds, void* workspace, size_t workspace_bytes, int* status, int* route,
+                                rk_stream_t stream);
 /* Workspace of one indexed decode, from HOST copies of the resident records and of pick: the m gathered records, the
  * per-segment table, then rk_jpeg_workspace_bytes of the picked records.  0 for a NULL table, m < 1 or max_segments < 1;
  * a pick outside [0, n) takes no frame region. */

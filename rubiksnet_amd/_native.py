@@ -170,6 +170,10 @@ SIGNATURES["rk_jpeg_decode_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _
 # htabs, nq, nh, n, entries, n_entries, entry_off, seg_mcus, build_status, pick, rgb_off, m, max_segments, rgb, rgb_bytes,
 # workspace, workspace_bytes, status, stream
 SIGNATURES["rk_jpeg_build_index"] = (_i, [_p, ctypes.c_longlong, _p, _p, _i, _i, _i, _p, _p, _p, ctypes.c_longlong, _p, _p])
+SIGNATURES["rk_jpeg_chunked_workspace_bytes"] = (_sz, [_p, _i, _i])
+# ... entries, n_entries, chunk_bytes, max_rounds, workspace, workspace_bytes, status, route, stream
+SIGNATURES["rk_jpeg_build_index_chunked"] = (_i, [_p, ctypes.c_longlong, _p, _p, _i, _i, _i, _p, _p, _p, ctypes.c_longlong, _i, _i,
+                                                  _p, _sz, _p, _p, _p])
 SIGNATURES["rk_jpeg_indexed_workspace_bytes"] = (_sz, [_p, _i, _p, _i, _i])
 SIGNATURES["rk_jpeg_decode_indexed_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _p, ctypes.c_longlong, _p, _p, _p, _p,
                                                 _p, _i, _i, _p, ctypes.c_longlong, _p, _sz, _p, _p])

@@ -25,6 +25,9 @@
 //                       plan, IDCT, colour and count run on them unchanged
 //   k_jpeg_entropy_seg  one wave (and one workgroup) per segment: resumes at its entry, must end at the next one
 //   k_jpeg_seg_status   a frame's code = that of its lowest failing segment
+//
+// rk_jpeg_build_index_chunked builds the same index from many short walks instead of one frame-long chain per frame
+// (k_jpeg_chunk_plan, k_jpeg_index_chunked, k_jpeg_index_chain; see below).
 #include "rk_common.hpp"
 #include "rk_jpeg_core.hpp"
 
@@ -138,12 +141,11 @@ __device__ __forceinline__ void load_tables(const rk_jpeg_frame& f, int ncomp, c
 
 // One wave per resident frame: the record and its row of the index checked from their own fields, then the one
 // sequential walk the frame ever gets, which stores no coefficient and writes the entry of every E-th MCU.
-__global__ __launch_bounds__(kWave) void k_jpeg_index(const unsigned char* __restrict__ streams, long long stream_bytes,
-                                                      const rk_jpeg_frame* __restrict__ frames,
-                                                      const rk_jpeg_huff* __restrict__ htabs, int nq, int nh,
-                                                      const int* __restrict__ seg_mcus, const long long* __restrict__ entry_off,
-                                                      rk_jpeg_entry* __restrict__ entries, long long n_entries,
-                                                      int* __restrict__ status) {
+__device__ __forceinline__ void index_frame(const unsigned char* __restrict__ streams, long long stream_bytes,
+                                            const rk_jpeg_frame* __restrict__ frames, const rk_jpeg_huff* __restrict__ htabs,
+                                            int nq, int nh, const int* __restrict__ seg_mcus,
+                                            const long long* __restrict__ entry_off, rk_jpeg_entry* __restrict__ entries,
+                                            long long n_entries, int* __restrict__ status) {
     __shared__ rk_jpeg_huff tabs[6];
     __shared__ unsigned char win[kJpegWindow];
     const int i = blockIdx.x, lane = threadIdx.x;
@@ -165,6 +167,239 @@ __global__ __launch_bounds__(kWave) void k_jpeg_index(const unsigned char* __res
     WindowSrc src{streams + f.stream_off, win, -(long long)kJpegWindow - 1, f.stream_len, lane};
     rc = rkjpeg::record_index(f, g, src, tabs, E, entries + first, lane == 0);
     if (lane == 0) status[i] = rc;
+}
+
+__global__ __launch_bounds__(kWave) void k_jpeg_index(const unsigned char* __restrict__ streams, long long stream_bytes,
+                                                      const rk_jpeg_frame* __restrict__ frames,
+                                                      const rk_jpeg_huff* __restrict__ htabs, int nq, int nh,
+                                                      const int* __restrict__ seg_mcus, const long long* __restrict__ entry_off,
+                                                      rk_jpeg_entry* __restrict__ entries, long long n_entries,
+                                                      int* __restrict__ status) {
+    index_frame(streams, stream_bytes, frames, htabs, nq, nh, seg_mcus, entry_off, entries, n_entries, status);
+}
+
+// ---------------------------------------------------------------------------------------------- the chunked index build
+// rk_jpeg_build_index_chunked (the scheme: rk_jpeg_core.hpp).  Four launches:
+//
+//   k_jpeg_chunk_plan     one workgroup: the frames' regions of the workspace (32 bytes per chunk) behind an offset table
+//   k_jpeg_index_chunked  one workgroup of 1024 lanes per frame; lane t walks chunks t, t + 1024, ...  The frame's tables sit
+//                         in LDS; every chunk's p_in, p_out and sums sit in the frame's region of the workspace, which
+//                         only this workgroup touches, always with a barrier between a store and another lane's load.
+//                         The rounds are separated by barriers in uniform control flow (a lane with nothing to walk
+//                         still reaches them); inside a walk the lanes diverge, each on a chain of its own that is one
+//                         chunk long.  Then the sums in front of every chunk, the final pass that writes the entries, and
+//                         route[i]: the rounds it took, or 0 where the frame is left to the next launch.
+//                         The stream is NOT staged in LDS: a walk reads its chunk as a few aligned 8-byte words, which
+//                         costs little beside the walk itself, while 40 KB of LDS per frame would leave a CU one
+//                         workgroup, every SIMD a few waves and nothing to hide the walks' latency with when a whole
+//                         set is built (profiles/jpeg_chunked_time.txt).
+//   k_jpeg_index_chain    the sequential walk of k_jpeg_index for the frames with route 0, and only for them
+//   k_jpeg_count
+constexpr int kChunkBlock = 1024;
+
+// The frame's stream read as aligned 8-byte words of which the lane keeps the last: a walk asks for consecutive bytes
+// (and for the one behind an FF), so seven of eight bytes cost no memory access.  A word that is not wholly inside
+// [streams, streams + stream_bytes) -- the arena's first or last -- is put together from the bytes that are.  No barrier
+// inside: the lanes diverge.
+struct WordSrc {
+    const unsigned char* mem;           // the frame's segment
+    uintptr_t lo, hi;                   // the arena: [streams, streams + stream_bytes)
+    uintptr_t at;                       // the address of the word held in `cur`, 0: none
+    unsigned long long cur;
+    __device__ __forceinline__ int byte(long long p) {
+        const uintptr_t addr = (uintptr_t)(mem + p), w = addr & ~(uintptr_t)7;
+        if (w != at) {
+            at = w;
+            if (w >= lo && w + 8 <= hi) {
+                cur = *reinterpret_cast<const unsigned long long*>(w);
+            } else {
+                cur = 0;
+                for (int k = 0; k < 8; ++k)
+                    if (w + k >= lo && w + k < hi) cur |= (unsigned long long)*reinterpret_cast<const unsigned char*>(w + k) << (8 * k);
+            }
+        }
+        return (int)(cur >> (((int)addr & 7) * 8)) & 0xFF;
+    }
+};
+
+struct ChunkState {                     // 32 bytes of the workspace per chunk
+    rkjpeg::ChunkSums sums;             // of the chunk's last walk; after the scan: of all chunks in front of it
+    int pin, pout;                      // bit positions (at most 8 * 512 * kMaxChunks); pout -1: the walk is dead
+    int dirty, reserved;                // p_in changed: the chunk is walked in the next round
+};
+static_assert(sizeof(ChunkState) == 32, "ChunkState is 32 bytes");
+
+__global__ __launch_bounds__(kBlock) void k_jpeg_chunk_plan(const rk_jpeg_frame* __restrict__ frames, int n, int S,
+                                                            long long* __restrict__ offsets) {
+    __shared__ long long part[kBlock];
+    const int t = threadIdx.x, per = (n + kBlock - 1) / kBlock;
+    const int lo = min(n, t * per), hi = min(n, lo + per);
+    long long sum = 0;
+    for (int i = lo; i < hi; ++i) sum += rkjpeg::chunk_count(frames[i], S);
+    part[t] = sum;
+    __syncthreads();
+    long long at = 0;
+    for (int k = 0; k < t; ++k) at += part[k];
+    for (int i = lo; i < hi; ++i) {
+        offsets[i] = rkjpeg::chunked_workspace_bytes(at, n);
+        at += rkjpeg::chunk_count(frames[i], S);
+    }
+    if (t == kBlock - 1) offsets[n] = rkjpeg::chunked_workspace_bytes(at, n);
+}
+
+struct ChunkShared {
+    int part[kChunkBlock][4], part_dead[kChunkBlock];
+    int changed[2], refused, finished;
+};
+
+// The rounds, the sums and the final pass of one frame; every lane of the workgroup calls it (barriers inside).
+// -> the rounds after which the walk had converged, 0 where the frame is left to the sequential walk.
+template <class Src>
+__device__ __forceinline__ int chunked_frame(const rk_jpeg_frame& f, const rkjpeg::Geometry& g, Src& src, const rk_jpeg_huff* tabs,
+                                             ChunkShared& sh, ChunkState* __restrict__ st, int nch, int S, int max_rounds, int E,
+                                             rk_jpeg_entry* __restrict__ row) {
+    const int t = threadIdx.x;
+    for (int c = t; c < nch; c += kChunkBlock) {
+        st[c].pin = 8 * c * S;
+        st[c].dirty = 1;
+    }
+    if (t == 0) sh.changed[0] = sh.changed[1] = sh.refused = sh.finished = 0;
+    __syncthreads();
+    int rounds = 0;
+    for (int r = 1; r <= max_rounds; ++r) {
+        for (int c = t; c < nch; c += kChunkBlock) {
+            if (!st[c].dirty) continue;
+            st[c].dirty = 0;
+            rkjpeg::ChunkSums own;
+            st[c].pout = (int)rkjpeg::walk_chunk(f, g, src, tabs, st[c].pin, 8LL * (c + 1) * S, own);
+            st[c].sums = own;
+        }
+        __syncthreads();                // the workgroup's own stores to global memory are visible to it behind a barrier
+        // Jacobi: every p_in comes from the round just walked.  This round's flag is changed[r & 1]; the other one, which
+        // every lane read before it came through the barrier above, is cleared for the next round.
+        if (t == 0) sh.changed[(r + 1) & 1] = 0;
+        for (int c = t; c < nch; c += kChunkBlock) {
+            const int want = (int)rkjpeg::chunk_next_in(c, S, c ? st[c - 1].pout : 0);
+            if (want != st[c].pin) {
+                st[c].pin = want;
+                st[c].dirty = 1;
+                sh.changed[r & 1] = 1;
+            }
+        }
+        __syncthreads();
+        if (!sh.changed[r & 1]) {       // the same word for every lane: uniform
+            rounds = r;
+            break;
+        }
+    }
+    if (rounds == 0) return 0;
+    // the sums in front of every chunk: each lane a run of consecutive chunks, then the lanes' totals
+    const int per = (nch + kChunkBlock - 1) / kChunkBlock;
+    const int lo = min(nch, t * per), hi = min(nch, lo + per);
+    unsigned a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    int dead = nch;
+    for (int c = hi - 1; c >= lo; --c) {
+        const rkjpeg::ChunkSums own = st[c].sums;
+        a0 += (unsigned)own.mcus;
+        a1 += (unsigned)own.dc0;
+        a2 += (unsigned)own.dc1;
+        a3 += (unsigned)own.dc2;
+        if (st[c].pout < 0) dead = c;
+    }
+    sh.part[t][0] = (int)a0;
+    sh.part[t][1] = (int)a1;
+    sh.part[t][2] = (int)a2;
+    sh.part[t][3] = (int)a3;
+    sh.part_dead[t] = dead;
+    __syncthreads();
+    a0 = a1 = a2 = a3 = 0;
+    const int used = min(kChunkBlock, (nch + per - 1) / per);   // the lanes whose runs are not empty
+    for (int k = 0; k < used; ++k) {
+        if (k < t) {
+            a0 += (unsigned)sh.part[k][0];
+            a1 += (unsigned)sh.part[k][1];
+            a2 += (unsigned)sh.part[k][2];
+            a3 += (unsigned)sh.part[k][3];
+        }
+        dead = min(dead, sh.part_dead[k]);      // the first dead walk: the sums in front of the chunks up to it are true
+    }
+    for (int c = lo; c < hi; ++c) {
+        const rkjpeg::ChunkSums own = st[c].sums;
+        st[c].sums = rkjpeg::ChunkSums{(int)a0, (int)a1, (int)a2, (int)a3};
+        a0 += (unsigned)own.mcus;
+        a1 += (unsigned)own.dc0;
+        a2 += (unsigned)own.dc1;
+        a3 += (unsigned)own.dc2;
+    }
+    __syncthreads();
+    for (int c = t; c < nch && c <= dead; c += kChunkBlock) {
+        const bool last = c + 1 == nch;
+        const rkjpeg::ChunkSums before = st[c].sums;
+        bool done = false;
+        const int rc = rkjpeg::index_chunk(f, g, src, tabs, st[c].pin, last ? f.stream_len * 8 + 1 : 8LL * (c + 1) * S,
+                                           last ? -1LL : (long long)st[c].pout, before, E, row, &done);
+        if (rc != RK_JPEG_OK) sh.refused = 1;
+        if (done) sh.finished = 1;
+    }
+    __syncthreads();
+    return sh.finished && !sh.refused ? rounds : 0;
+}
+
+// 8 waves per SIMD asked for: at most 64 VGPRs, so that two workgroups of 16 waves share a CU when a whole set is built.
+__global__ __launch_bounds__(kChunkBlock, 8) void k_jpeg_index_chunked(
+    const unsigned char* __restrict__ streams, long long stream_bytes, const rk_jpeg_frame* __restrict__ frames,
+    const rk_jpeg_huff* __restrict__ htabs, int nq, int nh, const int* __restrict__ seg_mcus,
+    const long long* __restrict__ entry_off, rk_jpeg_entry* __restrict__ entries, long long n_entries, int S, int max_rounds,
+    unsigned char* __restrict__ ws, long long ws_bytes, int* __restrict__ status, int* __restrict__ route) {
+    __shared__ rk_jpeg_huff tabs[6];
+    __shared__ ChunkShared sh;
+    const int i = blockIdx.x, t = threadIdx.x;
+    const rk_jpeg_frame f = frames[i];
+    rkjpeg::Geometry g;
+    const int E = seg_mcus[i];
+    const long long first = entry_off[i], last = entry_off[i + 1];
+    const long long ws_lo = reinterpret_cast<const long long*>(ws)[i], ws_hi = reinterpret_cast<const long long*>(ws)[i + 1];
+    const int nch = rkjpeg::chunk_count(f, S);
+    // what is not plainly a frame for this kernel is the sequential walk's, with the code it gives (uniform: one record)
+    bool mine = max_rounds > 0 && nch > 0 && rkjpeg::check_resident(f, stream_bytes, nq, nh) == RK_JPEG_OK;
+    if (mine) {
+        rkjpeg::geometry(f, g);
+        mine = rkjpeg::index_row_ok(g, E, first, last, n_entries) && ws_hi - ws_lo == 32LL * nch && ws_hi <= ws_bytes;
+    }
+    if (!mine) {
+        if (t == 0) route[i] = 0;
+        return;
+    }
+    constexpr int kWords = sizeof(rk_jpeg_huff) / 4;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                       // unrolled: f.dc[c] with a run-time c would put the record in scratch
+        if (c >= g.ncomp) break;
+        const unsigned* d = reinterpret_cast<const unsigned*>(htabs + f.dc[c]);
+        const unsigned* a = reinterpret_cast<const unsigned*>(htabs + f.ac[c]);
+        for (int k = t; k < kWords; k += kChunkBlock) {
+            reinterpret_cast<unsigned*>(&tabs[c])[k] = d[k];
+            reinterpret_cast<unsigned*>(&tabs[3 + c])[k] = a[k];
+        }
+    }
+    __syncthreads();
+    WordSrc src{streams + f.stream_off, (uintptr_t)streams, (uintptr_t)(streams + stream_bytes), 0, 0ull};
+    const int rounds = chunked_frame(f, g, src, tabs, sh, reinterpret_cast<ChunkState*>(ws + ws_lo), nch, S, max_rounds, E,
+                                     entries + first);
+    if (t == 0) {
+        route[i] = rounds;
+        if (rounds) status[i] = RK_JPEG_OK;
+    }
+}
+
+__global__ __launch_bounds__(kWave) void k_jpeg_index_chain(const unsigned char* __restrict__ streams, long long stream_bytes,
+                                                            const rk_jpeg_frame* __restrict__ frames,
+                                                            const rk_jpeg_huff* __restrict__ htabs, int nq, int nh,
+                                                            const int* __restrict__ seg_mcus,
+                                                            const long long* __restrict__ entry_off,
+                                                            rk_jpeg_entry* __restrict__ entries, long long n_entries,
+                                                            int* __restrict__ status, const int* __restrict__ route) {
+    if (route[blockIdx.x] != 0) return;                 // uniform: the chunked walk has written the frame's entries and code
+    index_frame(streams, stream_bytes, frames, htabs, nq, nh, seg_mcus, entry_off, entries, n_entries, status);
 }
 
 // The m picked records, each with its own place in the RGB arena, into the head of the workspace: from here on the
@@ -352,6 +587,39 @@ int rk_jpeg_build_index(const unsigned char* streams, long long stream_bytes, co
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_jpeg_index, dim3(n), dim3(kWave), 0, s, streams, stream_bytes, frames, htabs, nq, nh, seg_mcus,
                        entry_off, entries, n_entries, status);
+    hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, n);
+    return launch_status();
+}
+
+size_t rk_jpeg_chunked_workspace_bytes(const rk_jpeg_frame* frames_host, int n, int chunk_bytes) {
+    if (!frames_host || n < 1 || !rkjpeg::chunk_bytes_ok(chunk_bytes)) return 0;
+    long long chunks = 0;
+    for (int i = 0; i < n; ++i) chunks += rkjpeg::chunk_count(frames_host[i], chunk_bytes);
+    return (size_t)rkjpeg::chunked_workspace_bytes(chunks, n);
+}
+
+int rk_jpeg_build_index_chunked(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                                const rk_jpeg_huff* htabs, int nq, int nh, int n, const int* seg_mcus,
+                                const long long* entry_off, rk_jpeg_entry* entries, long long n_entries, int chunk_bytes,
+                                int max_rounds, void* workspace, size_t workspace_bytes, int* status, int* route,
+                                rk_stream_t stream) {
+    using namespace rk;
+    if (!streams || !frames || !htabs || !seg_mcus || !entry_off || !entries || !status || !route) return RK_ERR_NULL_POINTER;
+    if (n < 1 || n > 65535 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || stream_bytes < 0 || n_entries < 0)
+        return RK_ERR_BAD_DIMS;
+    if (!rkjpeg::chunk_bytes_ok(chunk_bytes) || max_rounds < 0 || max_rounds > 64) return RK_ERR_BAD_DIMS;
+    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)status & 3) || ((uintptr_t)seg_mcus & 3) ||
+        ((uintptr_t)entry_off & 7) || ((uintptr_t)entries & 7) || ((uintptr_t)route & 3))
+        return RK_ERR_BAD_DIMS;
+    if (!workspace || ((uintptr_t)workspace & 15) || (long long)workspace_bytes < rkjpeg::offset_table_bytes(n))
+        return RK_ERR_WORKSPACE;
+    const hipStream_t s = (hipStream_t)stream;
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    hipLaunchKernelGGL(k_jpeg_chunk_plan, dim3(1), dim3(kBlock), 0, s, frames, n, chunk_bytes, reinterpret_cast<long long*>(ws));
+    hipLaunchKernelGGL(k_jpeg_index_chunked, dim3(n), dim3(kChunkBlock), 0, s, streams, stream_bytes, frames, htabs, nq, nh, seg_mcus,
+                       entry_off, entries, n_entries, chunk_bytes, max_rounds, ws, (long long)workspace_bytes, status, route);
+    hipLaunchKernelGGL(k_jpeg_index_chain, dim3(n), dim3(kWave), 0, s, streams, stream_bytes, frames, htabs, nq, nh, seg_mcus,
+                       entry_off, entries, n_entries, status, route);
     hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, n);
     return launch_status();
 }

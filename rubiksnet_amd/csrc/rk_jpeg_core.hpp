@@ -1,8 +1,9 @@
 // rk_jpeg_core.hpp -- the baseline JPEG decode core of rk_jpeg.hip as plain host/device C++: record check and
 // geometry, bit reader, Huffman step, one scan's entropy decode -- whole, or a span of MCUs resumed at a recorded entry,
-// and the walk that records those entries -- jidctint's ISLOW IDCT, fancy upsampling and YCbCr -> RGB.  The kernels only
-// distribute this code over lanes; tests/jpeg_core_main.cpp and tests/jpeg_index_main.cpp compile the same text for the
-// CPU under AddressSanitizer / UBSan, which is the bounds proof for the kernels' logic.
+// the walk that records those entries, and the same entries from many short walks in lock-step rounds -- jidctint's ISLOW
+// IDCT, fancy upsampling and YCbCr -> RGB.  The kernels only distribute this code over lanes; tests/jpeg_core_main.cpp,
+// tests/jpeg_index_main.cpp and tests/jpeg_chunked_main.cpp compile the same text for the CPU under AddressSanitizer /
+// UBSan, which is the bounds proof for the kernels' logic.
 //
 // Every function is bounded by counts from the record and reads the stream through a source object that the caller
 // bounds; arithmetic that a hostile stream could overflow is done in unsigned (two's complement wrap, as the hardware).
@@ -408,6 +409,147 @@ RKJ_HD int record_index(const rk_jpeg_frame& f, const Geometry& g, Src& src, con
     NullSink sink;
     EntryRecorder rec{out, E, 0, writer};
     return walk_span<true>(f, g, src, tabs, sink, rec, zero, 0, (long long)g.mcux * g.mcuy, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ the chunked index build
+// The same index without the frame-long chain (rk_jpeg_build_index_chunked).  A frame without restart markers is cut into
+// chunks of S raw bytes; chunk c covers the bit positions [8 c S, 8 (c + 1) S).  A WALK of chunk c takes a position p_in
+// to be the start of an MCU and decodes whole MCUs until the first MCU boundary at or past the chunk's end, p_out; its
+// state is that one position, because a walk stops at MCU boundaries only.  Rounds in lock-step: in round 1 every chunk
+// starts at its own first bit, in round r + 1 at p_out of the chunk before it from round r (its own first bit again
+// where that walk was refused: a refusal must not travel down the frame).  Chunk 0 always starts at bit 0, the true
+// start, so by induction chunks 0 .. r - 1 hold the sequential walk's positions after round r: a fixed point IS the
+// sequential walk, and Huffman streams fall into step so quickly that it is reached in a few rounds, not in nchunks.
+// The MCU counts and DC sums of the walks, summed over the chunks in front, then give every chunk its first MCU
+// number and predictors, and a final pass walks each chunk once more and writes the entries.
+constexpr int kMaxChunks = 4096;        // the largest chunk count of a frame that takes the chunked route
+
+RKJ_HD bool chunk_bytes_ok(int S) { return S == 16 || S == 32 || S == 64 || S == 128 || S == 256 || S == 512; }
+
+// Chunks of the frame at S bytes each; 0 where the frame takes the sequential chain whatever its contents: restart
+// markers, an empty segment, more than kMaxChunks chunks.  From two fields alone, so that the host can size the workspace.
+RKJ_HD int chunk_count(const rk_jpeg_frame& f, int S) {
+    if (f.restart_interval != 0 || f.stream_len < 1 || f.stream_len > (long long)S * kMaxChunks) return 0;
+    return (int)((f.stream_len + S - 1) / S);
+}
+// Workspace of the chunked build: an offset table like the decoder's, then 32 bytes per chunk (its positions and sums).
+RKJ_HD long long chunked_workspace_bytes(long long total_chunks, int n) { return offset_table_bytes(n) + total_chunks * 32; }
+
+struct ChunkSums {          // of one walk: MCUs completed, DC differences added up per component (wrapping; see index_chunk)
+    int mcus, dc0, dc1, dc2;
+};
+
+// One MCU with nothing stored: every refusal of walk_span's loop body, in its order.  p0..p2 are running sums of the DC
+// differences; kRange: they are the true predictors and must stay inside +-2047.
+template <bool kRange, class Src>
+RKJ_HD int skip_mcu(BitReader<Src, true>& br, const Geometry& g, int nluma, const rk_jpeg_huff* tabs, int& p0, int& p1, int& p2) {
+    for (int j = 0; j < g.bpm; ++j) {
+        const int c = j < nluma ? 0 : j - nluma + 1;
+        int s = huff_symbol(br, tabs[c]);
+        if (s < 0) return RK_JPEG_BAD_CODE;
+        if (s > 11) return RK_JPEG_BAD_VALUE;
+        int dcv = c == 0 ? p0 : (c == 1 ? p1 : p2);
+        if (s) dcv = (int)((unsigned)dcv + (unsigned)receive_extend(br, s));
+        if (kRange && (dcv < -2047 || dcv > 2047)) return RK_JPEG_BAD_VALUE;
+        p0 = c == 0 ? dcv : p0;
+        p1 = c == 1 ? dcv : p1;
+        p2 = c == 2 ? dcv : p2;
+        int k = 1;
+        for (int guard = 0; guard < 63 && k < 64; ++guard) {
+            const int rs = huff_symbol(br, tabs[3 + c]);
+            if (rs < 0) return RK_JPEG_BAD_CODE;
+            const int r = rs >> 4;
+            s = rs & 15;
+            if (s == 0) {
+                if (r != 15) break;
+                k += 16;
+                if (k > 63) return RK_JPEG_BAD_RUN;
+                continue;
+            }
+            k += r;
+            if (k > 63) return RK_JPEG_BAD_RUN;
+            if (s > 10) return RK_JPEG_BAD_VALUE;
+            (void)receive_extend(br, s);
+            ++k;
+        }
+        if (br.overrun()) return RK_JPEG_TRUNCATED;
+    }
+    return RK_JPEG_OK;
+}
+
+// A speculative walk of one chunk from p_in (0 <= p_in <= 8 * stream_len) -> p_out, or -1 where the walk is DEAD: any
+// refusal, or a bit used past the end or past a marker.  p_in at or past end_bit passes through: p_out = p_in, no MCU.
+// Every MCU moves the position on by at least two bits or is refused: at most ceil(bits / 2) MCUs start inside the chunk,
+// and one more look at the position ends the loop.
+template <class Src>
+RKJ_HD long long walk_chunk(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, long long p_in,
+                            long long end_bit, ChunkSums& sums) {
+    sums.mcus = sums.dc0 = sums.dc1 = sums.dc2 = 0;
+    if (p_in >= end_bit) return p_in;
+    const int nluma = g.ncomp == 1 ? 1 : g.hs * g.vs;
+    BitReader<Src, true> br(src, f.stream_len);
+    br.seek(p_in);
+    for (long long guard = (end_bit - p_in + 1) / 2 + 1; guard > 0; --guard) {
+        const long long pos = br.bit_pos();
+        if (pos >= end_bit) return pos;
+        if (skip_mcu<false>(br, g, nluma, tabs, sums.dc0, sums.dc1, sums.dc2) != RK_JPEG_OK) return -1;
+        ++sums.mcus;
+    }
+    return -1;
+}
+
+// Where chunk c starts in the next round, given the chunk before it ended at prev_out in this one.
+RKJ_HD long long chunk_next_in(int c, int S, long long prev_out) {
+    return c == 0 ? 0 : (prev_out >= 0 ? prev_out : 8LL * c * S);
+}
+
+// The final pass over one chunk of a converged frame: p_in is its true start, `before` what the chunks in front of it
+// add up to -- its first MCU number and, DC differences being what predictors are sums of, its predictors.  (The sums
+// wrap; where every chunk in front kept its predictors inside +-2047, which each checks here, the wrapped sum is the
+// true one.)  Writes out[m / E] for every MCU m with m % E == 0 that starts in the chunk (out: the frame's row of the
+// index; m < nmcu, so the row holds it).  The chunk in which MCU nmcu - 1 ends applies BitReader::finish() there and
+// reports it in *finished; a chunk that starts at or past MCU nmcu has nothing to do.  Any other chunk must end exactly
+// at expect_out, the next chunk's start.  end_bit of the last chunk: past 8 * stream_len, which no position reaches.
+// Returns RK_JPEG_OK or the refusal; the frame has taken the chunked route only if no chunk refused and one finished.
+template <class Src>
+RKJ_HD int index_chunk(const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs, long long p_in,
+                       long long end_bit, long long expect_out, const ChunkSums& before, int E, rk_jpeg_entry* out,
+                       bool* finished) {
+    const long long nmcu = (long long)g.mcux * g.mcuy;
+    long long m = before.mcus;
+    if (m < 0) return RK_JPEG_BAD_INDEX;
+    if (m >= nmcu) return RK_JPEG_OK;
+    if (p_in >= end_bit) return p_in == expect_out ? RK_JPEG_OK : RK_JPEG_BAD_INDEX;
+    int p0 = before.dc0, p1 = before.dc1, p2 = before.dc2;
+    if (p0 < -2047 || p0 > 2047 || p1 < -2047 || p1 > 2047 || p2 < -2047 || p2 > 2047) return RK_JPEG_BAD_VALUE;
+    if (p_in < 0 || p_in > f.stream_len * 8 || E < 1) return RK_JPEG_BAD_INDEX;
+    const int nluma = g.ncomp == 1 ? 1 : g.hs * g.vs;
+    BitReader<Src, true> br(src, f.stream_len);
+    br.seek(p_in);
+    long long until = (E - m % E) % E;                      // MCUs until the next entry
+    rk_jpeg_entry* at = out + (m + E - 1) / E;
+    for (long long guard = (end_bit - p_in + 1) / 2 + 1; guard > 0; --guard) {
+        const long long pos = br.bit_pos();
+        if (pos >= end_bit) return pos == expect_out ? RK_JPEG_OK : RK_JPEG_BAD_INDEX;
+        if (until == 0) {
+            at->bit_pos = pos;
+            at->pred[0] = (short)p0;
+            at->pred[1] = (short)p1;
+            at->pred[2] = (short)p2;
+            at->reserved = 0;
+            ++at;
+            until = E;
+        }
+        --until;
+        const int rc = skip_mcu<true>(br, g, nluma, tabs, p0, p1, p2);
+        if (rc != RK_JPEG_OK) return rc;
+        if (++m == nmcu) {
+            const int end = br.finish();
+            *finished = end == RK_JPEG_OK;
+            return end;
+        }
+    }
+    return RK_JPEG_BAD_INDEX;
 }
 
 // ------------------------------------------------------------------------------------------------ IDCT

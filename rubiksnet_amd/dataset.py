@@ -12,7 +12,8 @@ device does the rest in one launch (augment.ragged_u8_to_clips, rk_clip_resample
   pack_clips        the collate function: arena [bytes], clips int64 [B, 4], labels
   FrameLoader       DataLoader workers -> pinned staging arena -> side-stream copy + ragged launch
                     (decode="device": the workers ship the JPEG files' bytes, jpeg.pack_jpeg_clips packs them and
-                    rk_jpeg_decode_u8 decodes them on the side stream in front of the ragged launch)
+                    rk_jpeg_decode_u8 decodes them on the side stream in front of the ragged launch; entropy="rows":
+                    by MCU row, through the chunked index build and rk_jpeg_decode_indexed_u8)
   DeviceFrameCache  a small set decoded once and resident in HBM; only the three small tables travel per batch
 
 The random draws come from a `torch.Generator` (or torch's global generator, which a DataLoader seeds per worker): the
@@ -399,19 +400,31 @@ class FrameLoader(_Feeder):
     decodes them into a per-slot RGB arena on the side stream, and the unchanged ragged launch follows on that arena.
     Boxes are drawn from the sizes in the headers, so nothing waits for the device; the clips are bit-identical to the
     host path's.  `fallback_frames` counts the frames that travelled decoded (files the device does not decode);
-    `decode_errors()` reads, on request, how many frames the device refused (they come out as zero frames)."""
+    `decode_errors()` reads, on request, how many frames the device refused (they come out as zero frames).
+    entropy="rows" (with decode="device") decodes by MCU row instead of one Huffman chain per frame: the index tables of a
+    batch's own records (jpeg.row_tables, made in the parent from the headers' sizes) travel with the blob,
+    rk_jpeg_build_index_chunked finds the rows' entries on the side stream and rk_jpeg_decode_indexed_u8 decodes by them,
+    in front of the same ragged launch; the clips are the same bits.  `chain_frames()` reads, on request, how many frames
+    the chunked build left to the sequential walk."""
 
     def __init__(self, dataset, batch, split, device="cuda:0", dtype=torch.float32, size=224, views=1, box_fn=None,
                  num_workers=0, depth=2, seed=0, temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5,
-                 decode="host"):
+                 decode="host", entropy="chain", chunk_bytes=256, max_rounds=32):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
+        if entropy not in ("chain", "rows"):
+            raise ValueError("entropy must be 'chain' or 'rows', got %r" % (entropy,))
+        if entropy == "rows" and decode != "device":
+            raise ValueError("entropy='rows' is a way to decode on the device: it goes with decode='device', not %r" % (decode,))
+        if entropy == "rows":
+            jpeg._check_chunking(chunk_bytes, max_rounds)
         if getattr(dataset, "decode", "host") != decode:
             raise ValueError("the dataset hands out %s-decoded samples, the loader was asked for decode=%r"
                              % (getattr(dataset, "decode", "host"), decode))
         self._init_feeder(dataset, batch, split, device, dtype, size, views, box_fn, temporal_clips, seed, flip_p)
         self.depth = int(depth)
         self.decode, self.fallback_frames = decode, 0
+        self.entropy, self.chunk_bytes, self.max_rounds = entropy, int(chunk_bytes), int(max_rounds)
         shuffle = (split == "train") if shuffle is None else shuffle
         self._dl = data.DataLoader(dataset, batch_size=self.batch, shuffle=shuffle, num_workers=num_workers,
                                    collate_fn=pack_clips if decode == "host" else jpeg.pack_jpeg_clips, drop_last=drop_last,
@@ -429,8 +442,10 @@ class FrameLoader(_Feeder):
             self._rgb = [None] * self.depth                # decoded frames, device
             self._ws = [None] * self.depth                 # the decoder's workspace, device
             self._status = [None] * self.depth             # its per-frame codes, device
+            self._rows = [None] * self.depth               # entropy="rows": entries, build workspace, build codes, route
             with torch.cuda.stream(self._stream):
                 self._errors = torch.zeros((), dtype=torch.int64, device=self.device)
+                self._chain = torch.zeros((), dtype=torch.int64, device=self.device)
         _mean_std_on(self.device, IMAGENET_MEAN, IMAGENET_STD)      # the one blocking upload happens here, not per batch
         for ev in self._consumed:
             ev.record(torch.cuda.current_stream(self.device))
@@ -461,6 +476,14 @@ class FrameLoader(_Feeder):
         self._stream.synchronize()
         return int(self._errors.item())
 
+    def chain_frames(self):
+        """entropy="rows": frames the chunked index build left to the sequential walk so far (restart intervals, no fixed
+        point within max_rounds, refused streams).  Waits for the side stream: ask once, at the end of an epoch."""
+        if self.decode != "device" or self.entropy != "rows":
+            return 0
+        self._stream.synchronize()
+        return int(self._chain.item())
+
     @staticmethod
     def _grown(t, need, make):
         """t if it holds `need` elements, else a new tensor with headroom (batches of a ragged set differ in size)."""
@@ -482,6 +505,12 @@ class FrameLoader(_Feeder):
             spots.append((nbytes, int(off), frame.numel()))
             nbytes += frame.numel()
         nj = int(packed.layout[0])
+        rows = None
+        if nj and self.entropy == "rows":                   # the batch's index tables travel behind the host-decoded frames
+            (host_frames, _, _, _), _ = jpeg.sections(packed.blob, packed.layout)
+            rows = jpeg.row_tables(np.frombuffer(host_frames.numpy(), dtype=jpeg.FRAME_DTYPE), self.chunk_bytes)
+            rows_at = nbytes = (nbytes + 15) & ~15
+            nbytes += rows.tables.numel()
         if self._copied[slot] is not None:
             self._copied[slot].synchronize()                # as in _launch: the copies that last read this slot are done
         if self._pinned[slot] is None or self._pinned[slot].numel() < nbytes:
@@ -493,14 +522,23 @@ class FrameLoader(_Feeder):
         with torch.cuda.stream(self._stream):
             self._rgb[slot] = self._grown(self._rgb[slot], rgb_bytes,
                                           lambda m: torch.empty(m, dtype=torch.uint8, device=self.device))
-            self._ws[slot] = self._grown(self._ws[slot], int(packed.workspace_bytes),
+            self._ws[slot] = self._grown(self._ws[slot], int(packed.workspace_bytes) if rows is None else rows.decode_bytes,
                                          lambda m: torch.empty(m, dtype=torch.uint8, device=self.device))
+            if rows is not None:
+                old = self._rows[slot] or (None, None, None, None)
+                self._rows[slot] = (
+                    self._grown(old[0], max(rows.n_entries, 1) * 2, lambda m: torch.empty(m, dtype=torch.int64, device=self.device)),
+                    self._grown(old[1], rows.build_bytes, lambda m: torch.empty(m, dtype=torch.uint8, device=self.device)),
+                    self._grown(old[2], nj + 1, lambda m: torch.zeros(m, dtype=torch.int32, device=self.device)),
+                    self._grown(old[3], nj, lambda m: torch.zeros(m, dtype=torch.int32, device=self.device)))
             self._status[slot] = self._grown(self._status[slot], nj + 1,
                                              lambda m: torch.zeros(m, dtype=torch.int32, device=self.device))
         host, dev = self._tables_for(slot, n, T)
         self._pinned[slot][:blob_bytes].copy_(packed.blob)
         for (at, _, m), (_, frame) in zip(spots, packed.fallback):
             self._pinned[slot][at:at + m].copy_(frame.reshape(-1))
+        if rows is not None:
+            self._pinned[slot][rows_at:nbytes].copy_(rows.tables)
         for name, t in (("clips", clips), ("frame_idx", frame_idx), ("boxes", boxes), ("labels", labels)):
             host[name][:t.shape[0]].copy_(t)
         self._host[slot] = {"packed": packed, "clips": clips, "frame_idx": frame_idx, "boxes": boxes, "labels": labels}
@@ -517,7 +555,14 @@ class FrameLoader(_Feeder):
             if nj:
                 (frames, htabs, qtabs, streams), (_, nh, nq) = jpeg.sections(self._arena[slot], packed.layout)
                 status = self._status[slot][:nj + 1]
-                jpeg.launch_decode(streams, frames, qtabs, htabs, nj, rgb, self._ws[slot], status, nq, nh)
+                if rows is None:
+                    jpeg.launch_decode(streams, frames, qtabs, htabs, nj, rgb, self._ws[slot], status, nq, nh)
+                else:
+                    entries, build_ws, build_status, route = self._rows[slot]
+                    jpeg.launch_decode_rows(streams, frames, qtabs, htabs, nq, nh, rows, self._arena[slot][rows_at:nbytes],
+                                            entries.view(torch.uint8), build_ws, build_status, route, rgb, self._ws[slot], status,
+                                            self.chunk_bytes, self.max_rounds)
+                    self._chain += (route[:nj] == 0).sum()
                 self._errors += status[nj]
             for at, off, m in spots:
                 rgb[off:off + m].copy_(self._arena[slot][at:at + m])
@@ -605,13 +650,21 @@ class DeviceFrameCache(_Feeder):
     entries, the host-decoded frames and one batch's RGB arena and workspace (grown on demand).  Files jpeg.parse_jpeg
     refuses are decoded once with Pillow, stay resident as RGB and are copied into place per batch (`fallback_frames`
     counts them); frames the index build refused come out as zero frames, `decode_errors()` reads how many such frames
-    went out so far.  A batch stays valid until the next one is asked for."""
+    went out so far.  index_build="chunked" (with resident="jpeg") builds the same index with
+    rk_jpeg_build_index_chunked instead of one frame-long walk per frame (jpeg.build_index(method="chunked")); `index.route`
+    says which frames took which way.  A batch stays valid until the next one is asked for."""
 
     def __init__(self, source, batch, split, device="cuda:0", dtype=torch.float32, size=224, views=1, box_fn=None, seed=0,
                  temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5, budget_bytes=4 << 30, resident="rgb",
-                 **sampling):
+                 index_build="chain", **sampling):
         if resident not in ("rgb", "jpeg"):
             raise ValueError("resident must be 'rgb' or 'jpeg', got %r" % (resident,))
+        if index_build not in ("chain", "chunked"):
+            raise ValueError("index_build must be 'chain' or 'chunked', got %r" % (index_build,))
+        if index_build == "chunked" and resident != "jpeg":
+            raise ValueError("index_build='chunked' builds the scan index of resident files: it goes with resident='jpeg', not "
+                             "%r" % (resident,))
+        self.index_build = index_build
         if resident == "jpeg" and not (isinstance(source, RubiksDataset) and source.decode == "device"):
             raise ValueError("resident='jpeg' keeps the files' bytes: it needs a RubiksDataset(..., decode='device'), not "
                              "%s" % ("in-memory videos, which are decoded already" if not isinstance(source, RubiksDataset)
@@ -655,11 +708,13 @@ class DeviceFrameCache(_Feeder):
         self._fallback_off = [0] + np.cumsum(sizes).tolist()
         n_entries = int(res.entry_off[-1])
         tables = res.seg_mcus.numel() * 4 + res.entry_off.numel() * 8 + (int(res.layout[0]) + 1) * 4
+        if self.index_build == "chunked":
+            tables += int(res.layout[0]) * 4                # the route array stays with the index
         self._fixed_bytes = res.blob.numel() + max(n_entries, 1) * 16 + tables + sum(sizes)
         if self._fixed_bytes > self.budget_bytes:
             raise RuntimeError("DeviceFrameCache: the %d videos take %d bytes as files, over the budget of %d bytes; raise "
                                "budget_bytes or stream with FrameLoader" % (len(source), self._fixed_bytes, self.budget_bytes))
-        self.index = jpeg.build_index(res, self.device)
+        self.index = jpeg.build_index(res, self.device, method=self.index_build)
         self._fallback = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
         for frame, at in zip(res.fallback, self._fallback_off):
             self._fallback[at:at + frame.numel()].copy_(frame.reshape(-1))

@@ -16,9 +16,14 @@ A set that stays on the device keeps its files' bytes there and is decoded by sc
 rk_jpeg_decode_indexed_u8; dataset.DeviceFrameCache(resident="jpeg")):
 
   pack_resident          a whole set as one blob + the index tables (one segment per MCU row by default)
-  build_index            upload + the one sequential walk every frame gets
+  build_index            upload + the one sequential walk every frame gets (method="chain"), or the same index from
+                         many short walks in lock-step rounds (method="chunked": rk_jpeg_build_index_chunked)
   pick_tables            per batch, on the host: which resident frames go where in the batch's RGB arena
   launch_decode_indexed  the launch on device tensors
+
+A streamed batch can take the row-parallel decoder too (decode_jpeg_frames(entropy="rows"), FrameLoader(entropy="rows")):
+row_tables makes the index tables of the batch's own records on the host, one segment per MCU row, the chunked build
+finds the entries on the device and rk_jpeg_decode_indexed_u8 decodes every record to its own place.
 
 There is no CPU path: a missing library is an error (tests compare with Pillow).
 """
@@ -31,7 +36,9 @@ import torch
 __all__ = ["JpegHeader", "parse_jpeg", "pack_jpeg_clips", "PackedJpeg", "decode_jpeg_frames", "launch_decode",
            "workspace_bytes_for", "huffman_record", "FRAME_DTYPE", "HUFF_DTYPE", "STATUS_NAMES", "MAX_SIDE", "ENTRY_DTYPE",
            "ResidentJpeg", "pack_resident", "DeviceIndex", "build_index", "PickTables", "pick_tables",
-           "frame_workspace_bytes", "indexed_workspace_bytes_for", "launch_decode_indexed"]
+           "frame_workspace_bytes", "indexed_workspace_bytes_for", "launch_decode_indexed", "chunked_workspace_bytes_for",
+           "launch_build_index_chunked", "RowTables", "row_tables", "launch_decode_rows", "CHUNK_BYTES", "MAX_ROUNDS",
+           "MAX_CHUNKS"]
 
 MAX_SIDE = 16384
 STATUS_NAMES = ("ok", "bad record", "bad code", "run past 63", "truncated", "bad restart", "trailing data", "bad value",
@@ -421,15 +428,67 @@ DeviceIndex = collections.namedtuple("DeviceIndex", [
     "blob", "frames", "htabs", "qtabs", "streams", "n", "nh", "nq",      # the resident blob on the device and its sections
     "seg_mcus", "entry_off", "entries", "n_entries",                     # int32 [n], int64 [n + 1], uint8 [n_entries * 16]
     "status",                                                            # int32 [n + 1]: the build's codes, [n] their count
-])
+    "route",                                                             # method="chunked": int32 [n], 0 where the sequential
+], defaults=(None,))                                                     # walk gave the frame's result, else the rounds; or None
+
+CHUNK_BYTES = (16, 32, 64, 128, 256, 512)                   # what rk_jpeg_build_index_chunked takes
+MAX_ROUNDS = 64
+MAX_CHUNKS = 4096                                           # a frame with more chunks takes the sequential walk
 
 
-def build_index(resident, device="cuda:0"):
-    """Upload a ResidentJpeg and walk every scan once (rk_jpeg_build_index, in chunks of 65535 frames, current stream).
-    Returns a DeviceIndex; nothing waits for the device."""
+def _check_chunking(chunk_bytes, max_rounds):
+    if chunk_bytes not in CHUNK_BYTES:
+        raise ValueError("chunk_bytes must be one of %r, got %r" % (CHUNK_BYTES, chunk_bytes))
+    if not 0 <= int(max_rounds) <= MAX_ROUNDS:
+        raise ValueError("max_rounds must be in [0, %d], got %r" % (MAX_ROUNDS, max_rounds))
+
+
+def chunked_workspace_bytes_for(frames, chunk_bytes):
+    """rk_jpeg_chunked_workspace_bytes of a FRAME_DTYPE array, in numpy: an offset table, then 32 bytes per chunk of every
+    frame that can take the chunked route (no restart interval, 1 .. MAX_CHUNKS chunks)."""
+    f = np.asarray(frames).reshape(-1)
+    if f.size < 1 or chunk_bytes not in CHUNK_BYTES:
+        return 0
+    length = f["stream_len"].astype(np.int64)
+    ok = (f["restart_interval"] == 0) & (length >= 1) & (length <= chunk_bytes * MAX_CHUNKS)
+    chunks = np.where(ok, (length + chunk_bytes - 1) // chunk_bytes, 0)
+    return (((f.size + 1) * 8 + 15) & ~15) + int(chunks.sum()) * 32
+
+
+def launch_build_index_chunked(streams, frames, htabs, nq, nh, n, seg_mcus, entry_off, entries, n_entries, chunk_bytes, max_rounds,
+                               workspace, status, route):
+    """rk_jpeg_build_index_chunked on the current stream.  Device tensors: streams, frames, htabs, entries (16-byte entries,
+    8-byte aligned), workspace (16-byte aligned) uint8; seg_mcus int32 [n], entry_off int64 [n + 1], status int32 [n + 1],
+    route int32 [n].  Nothing is allocated and the host does not wait."""
+    from . import _native
+    for name, t, dt in (("streams", streams, torch.uint8), ("frames", frames, torch.uint8), ("htabs", htabs, torch.uint8),
+                        ("entries", entries, torch.uint8), ("workspace", workspace, torch.uint8), ("seg_mcus", seg_mcus, torch.int32),
+                        ("entry_off", entry_off, torch.int64), ("status", status, torch.int32), ("route", route, torch.int32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor on the GPU" % (name, dt))
+    _check_chunking(chunk_bytes, max_rounds)
+    if frames.numel() < n * 64 or seg_mcus.numel() < n or entry_off.numel() < n + 1 or status.numel() < n + 1 or route.numel() < n:
+        raise ValueError("frames, seg_mcus, entry_off, status or route is shorter than n = %d asks for" % n)
+    if entries.numel() < n_entries * ENTRY_DTYPE.itemsize or htabs.numel() < nh * HUFF_DTYPE.itemsize:
+        raise ValueError("the entries or the table arena are shorter than n_entries / nh say")
+    _native.launch("rk_jpeg_build_index_chunked", streams.device, streams.data_ptr(), streams.numel(), frames.data_ptr(),
+                   htabs.data_ptr(), nq, nh, n, seg_mcus.data_ptr(), entry_off.data_ptr(), entries.data_ptr(), n_entries,
+                   int(chunk_bytes), int(max_rounds), workspace.data_ptr(), workspace.numel(), status.data_ptr(), route.data_ptr())
+
+
+def build_index(resident, device="cuda:0", method="chain", chunk_bytes=256, max_rounds=32):
+    """Upload a ResidentJpeg and build its scan index (in chunks of 65535 frames, current stream).  method="chain": the one
+    sequential walk per frame of rk_jpeg_build_index.  method="chunked": rk_jpeg_build_index_chunked -- walks of chunk_bytes
+    each in lock-step rounds, at most max_rounds of them, the sequential walk for the frames that do not take that route;
+    the same entries and codes, and `route` says which frames went which way.  Returns a DeviceIndex; nothing waits for
+    the device."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("build_index runs on a GPU (no CPU path)")
+    if method not in ("chain", "chunked"):
+        raise ValueError("method must be 'chain' or 'chunked', got %r" % (method,))
+    if method == "chunked":
+        _check_chunking(chunk_bytes, max_rounds)
     from . import _native
     blob = resident.blob.to(device)
     (frames, htabs, qtabs, streams), (n, nh, nq) = sections(blob, resident.layout)
@@ -437,15 +496,24 @@ def build_index(resident, device="cuda:0"):
     seg_mcus, entry_off = resident.seg_mcus.to(device), resident.entry_off.to(device)
     entries = torch.zeros(max(n_entries, 1) * ENTRY_DTYPE.itemsize // 8, dtype=torch.int64, device=device).view(torch.uint8)
     status = torch.zeros(n + 1, dtype=torch.int32, device=device)
+    route = torch.zeros(n, dtype=torch.int32, device=device) if method == "chunked" else None
+    if method == "chunked":
+        (host_frames, _, _, _), _ = sections(resident.blob, resident.layout)
+        rec = np.frombuffer(host_frames.numpy(), dtype=FRAME_DTYPE)
     for lo in range(0, n, MAX_LAUNCH):
         k = min(MAX_LAUNCH, n - lo)
         part = torch.zeros(k + 1, dtype=torch.int32, device=device)
-        _native.launch("rk_jpeg_build_index", device, streams.data_ptr(), streams.numel(),
-                       frames[lo * 64:].data_ptr(), htabs.data_ptr(), nq, nh, k, seg_mcus[lo:].data_ptr(),
-                       entry_off[lo:].data_ptr(), entries.data_ptr(), n_entries, part.data_ptr())
+        if method == "chunked":
+            ws = torch.empty(chunked_workspace_bytes_for(rec[lo:lo + k], chunk_bytes), dtype=torch.uint8, device=device)
+            launch_build_index_chunked(streams, frames[lo * 64:], htabs, nq, nh, k, seg_mcus[lo:], entry_off[lo:], entries, n_entries,
+                                       chunk_bytes, max_rounds, ws, part, route[lo:])
+        else:
+            _native.launch("rk_jpeg_build_index", device, streams.data_ptr(), streams.numel(),
+                           frames[lo * 64:].data_ptr(), htabs.data_ptr(), nq, nh, k, seg_mcus[lo:].data_ptr(),
+                           entry_off[lo:].data_ptr(), entries.data_ptr(), n_entries, part.data_ptr())
         status[lo:lo + k].copy_(part[:k])
         status[n] += part[k]
-    return DeviceIndex(blob, frames, htabs, qtabs, streams, n, nh, nq, seg_mcus, entry_off, entries, n_entries, status)
+    return DeviceIndex(blob, frames, htabs, qtabs, streams, n, nh, nq, seg_mcus, entry_off, entries, n_entries, status, route)
 
 
 PickTables = collections.namedtuple("PickTables", [
@@ -541,20 +609,96 @@ def sections(blob, layout):
             blob[o_quant:o_quant + nq * 128], blob[o_stream:o_stream + stream_bytes]), (n, nh, nq)
 
 
-def decode_jpeg_frames(packed, device="cuda:0", out=None, workspace=None):
+# ------------------------------------------------------------------------------------------------- a streamed batch by rows
+RowTables = collections.namedtuple("RowTables", [
+    "tables",           # uint8: seg_mcus int32 [n] | entry_off int64 [n + 1] | pick int32 [n] | rgb_off int64 [n], 16-byte aligned
+    "offsets",          # the four sections' byte offsets in `tables`
+    "n", "n_entries", "max_segments",
+    "build_bytes",      # rk_jpeg_chunked_workspace_bytes of the records
+    "decode_bytes",     # rk_jpeg_indexed_workspace_bytes of the records, each picked once
+])
+
+
+def row_tables(frames, chunk_bytes=256):
+    """The index tables of a batch's own records, on the host (a FRAME_DTYPE array; n >= 1): one segment per MCU row --
+    seg_mcus is the MCUs per row and entry_off its rows' exclusive sum -- every record picked once, in order, to its own
+    rgb_off; and the two workspace sizes, in numpy (a DataLoader worker does not load the HIP library).  A record whose
+    sizes are not valid gets one segment of one MCU; the build refuses it from its fields."""
+    f = np.asarray(frames).reshape(-1)
+    n = f.size
+    w, h, nc, s = (f[k].astype(np.int64) for k in ("width", "height", "components", "sampling"))
+    ok = (w >= 1) & (w <= MAX_SIDE) & (h >= 1) & (h <= MAX_SIDE) & ((nc == 1) | ((nc == 3) & (s >= 0) & (s <= 2)))
+    hs, vs = np.where((nc == 3) & (s >= 1), 2, 1), np.where((nc == 3) & (s == 2), 2, 1)
+    mcux = np.where(ok, (w + 8 * hs - 1) // (8 * hs), 1)
+    mcuy = np.where(ok, (h + 8 * vs - 1) // (8 * vs), 1)
+    entry_off = np.concatenate([[0], np.cumsum(mcuy)]).astype(np.int64)
+    parts = (mcux.astype(np.int32), entry_off, np.arange(n, dtype=np.int32), f["rgb_off"].astype(np.int64))
+    offsets, at = [], 0
+    for part in parts:
+        offsets.append(at)
+        at = _align16(at + part.nbytes)
+    tables = np.zeros(at, dtype=np.uint8)
+    for off, part in zip(offsets, parts):
+        tables[off:off + part.nbytes] = part.view(np.uint8)
+    most = int(mcuy.max())
+    return RowTables(torch.from_numpy(tables), tuple(offsets), n, int(entry_off[-1]), most,
+                     chunked_workspace_bytes_for(f, chunk_bytes), indexed_workspace_bytes_for(f, parts[2], most))
+
+
+def launch_decode_rows(streams, frames, qtabs, htabs, nq, nh, rows, tables, entries, build_ws, build_status, route, rgb,
+                       decode_ws, status, chunk_bytes=256, max_rounds=32):
+    """A batch decoded by MCU row on the current stream: rk_jpeg_build_index_chunked over the batch's own records, then
+    rk_jpeg_decode_indexed_u8 of every record to its own place.  rows: row_tables of the records; tables: rows.tables on
+    the device (16-byte aligned); entries uint8 [rows.n_entries * 16] (8-byte aligned), build_ws / decode_ws uint8
+    (rows.build_bytes / rows.decode_bytes, 16-byte aligned), build_status int32 [n + 1], route int32 [n], status int32
+    [n + 1]: device tensors.  Eleven launches, one linear chain; nothing is allocated and the host does not wait."""
+    n = rows.n
+    o_seg, o_off, o_pick, o_rgb = rows.offsets
+    seg_mcus = tables[o_seg:o_seg + 4 * n].view(torch.int32)
+    entry_off = tables[o_off:o_off + 8 * (n + 1)].view(torch.int64)
+    pick = tables[o_pick:o_pick + 4 * n].view(torch.int32)
+    rgb_off = tables[o_rgb:o_rgb + 8 * n].view(torch.int64)
+    launch_build_index_chunked(streams, frames, htabs, nq, nh, n, seg_mcus, entry_off, entries, rows.n_entries, chunk_bytes,
+                               max_rounds, build_ws, build_status, route)
+    index = DeviceIndex(None, frames, htabs, qtabs, streams, n, nh, nq, seg_mcus, entry_off, entries, rows.n_entries,
+                        build_status, route)
+    launch_decode_indexed(index, pick, rgb_off, rows.max_segments, rgb, decode_ws, status)
+
+
+def decode_jpeg_frames(packed, device="cuda:0", out=None, workspace=None, entropy="chain", chunk_bytes=256, max_rounds=32):
     """Decode one packed batch on `device` (current stream).  Returns (rgb arena uint8 [rgb_bytes], clips, status int32
     [n + 1]): the arena and `clips` are what augment.ragged_u8_to_clips takes.  out / workspace: device uint8 tensors to
     use (at least rgb_bytes / workspace_bytes long).  Frames that travelled as RGB are copied into the arena; status
-    covers the device-decoded frames in order, status[n] counts those that failed (zero frames)."""
+    covers the device-decoded frames in order, status[n] counts those that failed (zero frames).
+    entropy="chain": rk_jpeg_decode_u8, one Huffman chain per frame.  entropy="rows": one chain per MCU row -- the scan
+    index of the batch's own records is built on the device by rk_jpeg_build_index_chunked (chunk_bytes, max_rounds) and
+    rk_jpeg_decode_indexed_u8 decodes by it; the same arena and the same codes.  workspace must then hold the
+    decoder's row_tables(...).decode_bytes; the build's buffers are allocated here."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("decode_jpeg_frames decodes on a GPU (no CPU path)")
+    if entropy not in ("chain", "rows"):
+        raise ValueError("entropy must be 'chain' or 'rows', got %r" % (entropy,))
+    if entropy == "rows":
+        _check_chunking(chunk_bytes, max_rounds)
     (frames, htabs, qtabs, streams), (n, nh, nq) = sections(packed.blob.to(device), packed.layout)
     rgb = torch.empty(packed.rgb_bytes, dtype=torch.uint8, device=device) if out is None else out[:packed.rgb_bytes]
     if rgb.numel() < packed.rgb_bytes:
         raise ValueError("out holds %d bytes, the batch decodes to %d" % (rgb.numel(), packed.rgb_bytes))
     status = torch.zeros(n + 1, dtype=torch.int32, device=device)
-    if n:
+    if n and entropy == "rows":
+        (host_frames, _, _, _), _ = sections(packed.blob, packed.layout)
+        rows = row_tables(np.frombuffer(host_frames.numpy(), dtype=FRAME_DTYPE), chunk_bytes)
+        if workspace is None:
+            workspace = torch.empty(rows.decode_bytes, dtype=torch.uint8, device=device)
+        elif workspace.numel() < rows.decode_bytes:
+            raise ValueError("workspace holds %d bytes, the decode by rows needs %d" % (workspace.numel(), rows.decode_bytes))
+        entries = torch.empty(max(rows.n_entries, 1) * 2, dtype=torch.int64, device=device).view(torch.uint8)
+        launch_decode_rows(streams, frames, qtabs, htabs, nq, nh, rows, rows.tables.to(device), entries,
+                           torch.empty(rows.build_bytes, dtype=torch.uint8, device=device),
+                           torch.zeros(n + 1, dtype=torch.int32, device=device), torch.zeros(n, dtype=torch.int32, device=device),
+                           rgb, workspace, status, chunk_bytes, max_rounds)
+    elif n:
         if workspace is None:
             workspace = torch.empty(packed.workspace_bytes, dtype=torch.uint8, device=device)
         launch_decode(streams, frames, qtabs, htabs, n, rgb, workspace, status, nq, nh)

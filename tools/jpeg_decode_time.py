@@ -11,7 +11,10 @@ every GPU step in a child process of its own under a time limit, three alternati
   3. the decode launch alone on 256 frames (events around back-to-back launches, median of 5 windows) and the ragged
      launch behind it;  4. a RubiksNet-Tiny training step fed by each path.
 --parent-dataset: a copy of the previous commit's rubiksnet_amd/dataset.py to take the host path from (the host path of
-this tree is that code behind one `if`).  The workers never open the GPU: at most one process does at a time."""
+this tree is that code behind one `if`).  The workers never open the GPU: at most one process does at a time.
+--chunked: only FrameLoader(decode="device") with entropy="rows" beside entropy="chain", at 8 and at 16 workers, three
+alternating runs; the lines are appended to --out (default profiles/jpeg_chunked_time.txt, behind what
+tools/jpeg_cache_time.py --chunked wrote)."""
 import argparse
 import importlib.util
 import json
@@ -58,17 +61,19 @@ def _dataset_module(parent):
     return mod
 
 
-def _loader(root, decode, workers, parent=None):
+def _loader(root, decode, workers, parent=None, entropy="chain"):
     import torch
     mod = _dataset_module(parent if decode == "host" else None)
     kw = {} if decode == "host" else {"decode": "device"}
     ds = mod.RubiksDataset(root, os.path.join(root, "list.txt"), num_segments=8, random_shift=True, **kw)
+    if entropy != "chain":
+        kw = dict(kw, entropy=entropy)
     return mod.FrameLoader(ds, 32, "train", dtype=torch.float32, size=224, num_workers=workers, seed=1, **kw)
 
 
 def child_loader(a):
     import torch
-    loader = _loader(a.root, a.decode, a.workers, a.parent_dataset)
+    loader = _loader(a.root, a.decode, a.workers, a.parent_dataset, a.entropy)
     handed, clips = [], 0
     for _ in loader:                                        # warm-up epoch: workers start, arenas grow
         pass
@@ -83,6 +88,8 @@ def child_loader(a):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     extra = {} if a.decode == "host" else {"fallback_frames": loader.fallback_frames, "decode_errors": loader.decode_errors()}
+    if a.entropy == "rows":
+        extra["chain_frames"] = loader.chain_frames()
     print(json.dumps(dict(clips_per_s=clips / dt, bytes_per_batch=statistics.mean(handed), **extra)))
 
 
@@ -166,7 +173,9 @@ def span(values, fmt="%.0f"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_time.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--chunked", action="store_true")
+    ap.add_argument("--entropy", default="chain")
     ap.add_argument("--videos", type=int, default=64)
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--epochs", type=int, default=12)
@@ -178,6 +187,7 @@ def main():
     a = ap.parse_args()
     if a.child:
         return {"loader": child_loader, "kernel": child_kernel, "train": child_train}[a.child](a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "jpeg_chunked_time.txt" if a.chunked else "jpeg_decode_time.txt")
     lines = []
 
     def say(text):
@@ -189,6 +199,19 @@ def main():
         mean_file = write_frames(root, a.videos, a.frames)
         say("%d videos x %d frames, 256 x 340, 4:2:0, quality 90: %.1f KB a file (decoded: 261.1 KB)"
             % (a.videos, a.frames, mean_file / 1000))
+        for workers in (8, 16) if a.chunked else ():
+            runs = {"chain": [], "rows": []}
+            for _ in range(3):
+                for entropy in runs:
+                    runs[entropy].append(run_child(a, "loader", 300, decode="device", workers=workers, entropy=entropy))
+            for entropy, r in runs.items():
+                say("loader  workers=%-2d decode=device entropy=%-5s clips/s %s   decode_errors %d%s"
+                    % (workers, entropy, span([x["clips_per_s"] for x in r]), r[0]["decode_errors"],
+                       "" if entropy == "chain" else "   frames left to the sequential walk %d" % r[0]["chain_frames"]))
+        if a.chunked:
+            with open(a.out, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
+            return
         say("host path: %s" % ("the previous commit's dataset.py" if a.parent_dataset else "this tree's decode='host'"))
         for workers in (8, 16):
             runs = {"host": [], "device": []}
