@@ -28,6 +28,8 @@
 //
 // rk_jpeg_build_index_chunked builds the same index from many short walks instead of one frame-long chain per frame
 // (k_jpeg_chunk_plan, k_jpeg_index_chunked, k_jpeg_index_chain; see below).
+#include <initializer_list>
+
 #include "rk_common.hpp"
 #include "rk_jpeg_core.hpp"
 
@@ -90,6 +92,29 @@ struct LaneSink {
         mine = 0;
     }
 };
+// The lane's sink onto frame i's coefficient region of the workspace.
+__device__ __forceinline__ LaneSink lane_sink(unsigned char* __restrict__ ws, int i, int lane) {
+    int zigzag = 0;
+    for (int k = 0; k < 64; ++k) zigzag = rkjpeg::natural_of(k) == lane ? k : zigzag;
+    return LaneSink{reinterpret_cast<short*>(ws + reinterpret_cast<const long long*>(ws)[i]), lane, zigzag, 0};
+}
+
+// The frame's six tables into LDS, DC of component c at [c], AC at [3 + c], by the `lanes` lanes of the workgroup (the
+// caller syncs).
+__device__ __forceinline__ void load_tables(const rk_jpeg_frame& f, int ncomp, const rk_jpeg_huff* __restrict__ htabs,
+                                            rk_jpeg_huff* tabs, int lane, int lanes) {
+    constexpr int kWords = sizeof(rk_jpeg_huff) / 4;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                       // unrolled: f.dc[c] with a run-time c would put the record in scratch
+        if (c >= ncomp) break;
+        const unsigned* d = reinterpret_cast<const unsigned*>(htabs + f.dc[c]);
+        const unsigned* a = reinterpret_cast<const unsigned*>(htabs + f.ac[c]);
+        for (int k = lane; k < kWords; k += lanes) {
+            reinterpret_cast<unsigned*>(&tabs[c])[k] = d[k];
+            reinterpret_cast<unsigned*>(&tabs[3 + c])[k] = a[k];
+        }
+    }
+}
 
 __global__ __launch_bounds__(kWave) void k_jpeg_entropy(const unsigned char* __restrict__ streams,
                                                         const rk_jpeg_frame* __restrict__ frames,
@@ -102,9 +127,10 @@ __global__ __launch_bounds__(kWave) void k_jpeg_entropy(const unsigned char* __r
     const rk_jpeg_frame f = frames[i];
     rkjpeg::Geometry g;
     rkjpeg::geometry(f, g);
+    // load_tables' text in place: through the call this kernel's table load comes out in another order than it had
     constexpr int kWords = sizeof(rk_jpeg_huff) / 4;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {                       // unrolled: f.dc[c] with a run-time c would put the record in scratch
+    for (int c = 0; c < 3; ++c) {
         if (c >= g.ncomp) break;
         const unsigned* d = reinterpret_cast<const unsigned*>(htabs + f.dc[c]);
         const unsigned* a = reinterpret_cast<const unsigned*>(htabs + f.ac[c]);
@@ -115,30 +141,12 @@ __global__ __launch_bounds__(kWave) void k_jpeg_entropy(const unsigned char* __r
     }
     __syncthreads();
     WindowSrc src{streams + f.stream_off, win, -(long long)kJpegWindow - 1, f.stream_len, lane};
-    int zigzag = 0;
-    for (int k = 0; k < 64; ++k) zigzag = rkjpeg::natural_of(k) == lane ? k : zigzag;
-    LaneSink sink{reinterpret_cast<short*>(ws + reinterpret_cast<const long long*>(ws)[i]), lane, zigzag, 0};
+    LaneSink sink = lane_sink(ws, i, lane);
     const int rc = rkjpeg::decode_scan(f, g, src, tabs, sink);
     if (lane == 0) status[i] = rc;
 }
 
 // ---------------------------------------------------------------------------------------------- the scan index
-// The frame's six tables into LDS, as k_jpeg_entropy loads them (one wave; the caller syncs).
-__device__ __forceinline__ void load_tables(const rk_jpeg_frame& f, int ncomp, const rk_jpeg_huff* __restrict__ htabs,
-                                            rk_jpeg_huff* tabs, int lane) {
-    constexpr int kWords = sizeof(rk_jpeg_huff) / 4;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (c >= ncomp) break;
-        const unsigned* d = reinterpret_cast<const unsigned*>(htabs + f.dc[c]);
-        const unsigned* a = reinterpret_cast<const unsigned*>(htabs + f.ac[c]);
-        for (int k = lane; k < kWords; k += kWave) {
-            reinterpret_cast<unsigned*>(&tabs[c])[k] = d[k];
-            reinterpret_cast<unsigned*>(&tabs[3 + c])[k] = a[k];
-        }
-    }
-}
-
 // One wave per resident frame: the record and its row of the index checked from their own fields, then the one
 // sequential walk the frame ever gets, which stores no coefficient and writes the entry of every E-th MCU.
 __device__ __forceinline__ void index_frame(const unsigned char* __restrict__ streams, long long stream_bytes,
@@ -162,7 +170,7 @@ __device__ __forceinline__ void index_frame(const unsigned char* __restrict__ st
         if (lane == 0) status[i] = rc;
         return;
     }
-    load_tables(f, g.ncomp, htabs, tabs, lane);
+    load_tables(f, g.ncomp, htabs, tabs, lane, kWave);
     __syncthreads();
     WindowSrc src{streams + f.stream_off, win, -(long long)kJpegWindow - 1, f.stream_len, lane};
     rc = rkjpeg::record_index(f, g, src, tabs, E, entries + first, lane == 0);
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(kWave) void k_jpeg_index(const unsigned char* __res
 //                         set is built (profiles/jpeg_chunked_time.txt).
 //   k_jpeg_index_chain    the sequential walk of k_jpeg_index for the frames with route 0, and only for them
 //   k_jpeg_count
-constexpr int kChunkBlock = 1024;
+using rkjpeg::kChunkBlock;
 
 // The frame's stream read as aligned 8-byte words of which the lane keeps the last: a walk asks for consecutive bytes
 // (and for the one behind an FF), so seven of eight bytes cost no memory access.  A word that is not wholly inside
@@ -222,13 +230,6 @@ struct WordSrc {
     }
 };
 
-struct ChunkState {                     // 32 bytes of the workspace per chunk
-    rkjpeg::ChunkSums sums;             // of the chunk's last walk; after the scan: of all chunks in front of it
-    int pin, pout;                      // bit positions (at most 8 * 512 * kMaxChunks); pout -1: the walk is dead
-    int dirty, reserved;                // p_in changed: the chunk is walked in the next round
-};
-static_assert(sizeof(ChunkState) == 32, "ChunkState is 32 bytes");
-
 __global__ __launch_bounds__(kBlock) void k_jpeg_chunk_plan(const rk_jpeg_frame* __restrict__ frames, int n, int S,
                                                             long long* __restrict__ offsets) {
     __shared__ long long part[kBlock];
@@ -247,102 +248,32 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_chunk_plan(const rk_jpeg_frame*
     if (t == kBlock - 1) offsets[n] = rkjpeg::chunked_workspace_bytes(at, n);
 }
 
-struct ChunkShared {
-    int part[kChunkBlock][4], part_dead[kChunkBlock];
-    int changed[2], refused, finished;
-};
-
-// The rounds, the sums and the final pass of one frame; every lane of the workgroup calls it (barriers inside).
+// The phases of rk_jpeg_core.hpp with a barrier behind each; every lane of the workgroup calls it, and the control flow
+// around the barriers is uniform (the words of `sh` that steer it are the same for every lane).
 // -> the rounds after which the walk had converged, 0 where the frame is left to the sequential walk.
 template <class Src>
 __device__ __forceinline__ int chunked_frame(const rk_jpeg_frame& f, const rkjpeg::Geometry& g, Src& src, const rk_jpeg_huff* tabs,
-                                             ChunkShared& sh, ChunkState* __restrict__ st, int nch, int S, int max_rounds, int E,
-                                             rk_jpeg_entry* __restrict__ row) {
+                                             rkjpeg::ChunkShared& sh, rkjpeg::ChunkState* __restrict__ st, int nch, int S,
+                                             int max_rounds, int E, rk_jpeg_entry* __restrict__ row) {
     const int t = threadIdx.x;
-    for (int c = t; c < nch; c += kChunkBlock) {
-        st[c].pin = 8 * c * S;
-        st[c].dirty = 1;
-    }
-    if (t == 0) sh.changed[0] = sh.changed[1] = sh.refused = sh.finished = 0;
+    rkjpeg::chunk_init(t, kChunkBlock, sh, st, nch, S);
     __syncthreads();
     int rounds = 0;
-    for (int r = 1; r <= max_rounds; ++r) {
-        for (int c = t; c < nch; c += kChunkBlock) {
-            if (!st[c].dirty) continue;
-            st[c].dirty = 0;
-            rkjpeg::ChunkSums own;
-            st[c].pout = (int)rkjpeg::walk_chunk(f, g, src, tabs, st[c].pin, 8LL * (c + 1) * S, own);
-            st[c].sums = own;
-        }
+    for (int r = 1; r <= max_rounds && !rounds; ++r) {
+        rkjpeg::chunk_walk_dirty(t, kChunkBlock, f, g, src, tabs, st, nch, S);
         __syncthreads();                // the workgroup's own stores to global memory are visible to it behind a barrier
-        // Jacobi: every p_in comes from the round just walked.  This round's flag is changed[r & 1]; the other one, which
-        // every lane read before it came through the barrier above, is cleared for the next round.
-        if (t == 0) sh.changed[(r + 1) & 1] = 0;
-        for (int c = t; c < nch; c += kChunkBlock) {
-            const int want = (int)rkjpeg::chunk_next_in(c, S, c ? st[c - 1].pout : 0);
-            if (want != st[c].pin) {
-                st[c].pin = want;
-                st[c].dirty = 1;
-                sh.changed[r & 1] = 1;
-            }
-        }
+        rkjpeg::chunk_advance(t, kChunkBlock, sh, st, nch, S, r);
         __syncthreads();
-        if (!sh.changed[r & 1]) {       // the same word for every lane: uniform
-            rounds = r;
-            break;
-        }
+        if (rkjpeg::chunk_converged(sh, r)) rounds = r;
     }
     if (rounds == 0) return 0;
-    // the sums in front of every chunk: each lane a run of consecutive chunks, then the lanes' totals
-    const int per = (nch + kChunkBlock - 1) / kChunkBlock;
-    const int lo = min(nch, t * per), hi = min(nch, lo + per);
-    unsigned a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    int dead = nch;
-    for (int c = hi - 1; c >= lo; --c) {
-        const rkjpeg::ChunkSums own = st[c].sums;
-        a0 += (unsigned)own.mcus;
-        a1 += (unsigned)own.dc0;
-        a2 += (unsigned)own.dc1;
-        a3 += (unsigned)own.dc2;
-        if (st[c].pout < 0) dead = c;
-    }
-    sh.part[t][0] = (int)a0;
-    sh.part[t][1] = (int)a1;
-    sh.part[t][2] = (int)a2;
-    sh.part[t][3] = (int)a3;
-    sh.part_dead[t] = dead;
+    rkjpeg::chunk_run_sums(t, kChunkBlock, sh, st, nch);
     __syncthreads();
-    a0 = a1 = a2 = a3 = 0;
-    const int used = min(kChunkBlock, (nch + per - 1) / per);   // the lanes whose runs are not empty
-    for (int k = 0; k < used; ++k) {
-        if (k < t) {
-            a0 += (unsigned)sh.part[k][0];
-            a1 += (unsigned)sh.part[k][1];
-            a2 += (unsigned)sh.part[k][2];
-            a3 += (unsigned)sh.part[k][3];
-        }
-        dead = min(dead, sh.part_dead[k]);      // the first dead walk: the sums in front of the chunks up to it are true
-    }
-    for (int c = lo; c < hi; ++c) {
-        const rkjpeg::ChunkSums own = st[c].sums;
-        st[c].sums = rkjpeg::ChunkSums{(int)a0, (int)a1, (int)a2, (int)a3};
-        a0 += (unsigned)own.mcus;
-        a1 += (unsigned)own.dc0;
-        a2 += (unsigned)own.dc1;
-        a3 += (unsigned)own.dc2;
-    }
+    const int dead = rkjpeg::chunk_sums_in_front(t, kChunkBlock, sh, st, nch);     // lane-local, the same in every lane
     __syncthreads();
-    for (int c = t; c < nch && c <= dead; c += kChunkBlock) {
-        const bool last = c + 1 == nch;
-        const rkjpeg::ChunkSums before = st[c].sums;
-        bool done = false;
-        const int rc = rkjpeg::index_chunk(f, g, src, tabs, st[c].pin, last ? f.stream_len * 8 + 1 : 8LL * (c + 1) * S,
-                                           last ? -1LL : (long long)st[c].pout, before, E, row, &done);
-        if (rc != RK_JPEG_OK) sh.refused = 1;
-        if (done) sh.finished = 1;
-    }
+    rkjpeg::chunk_final_pass(t, kChunkBlock, f, g, src, tabs, sh, st, nch, S, E, row, dead);
     __syncthreads();
-    return sh.finished && !sh.refused ? rounds : 0;
+    return rkjpeg::chunk_route(sh, rounds);
 }
 
 // 8 waves per SIMD asked for: at most 64 VGPRs, so that two workgroups of 16 waves share a CU when a whole set is built.
@@ -352,7 +283,7 @@ __global__ __launch_bounds__(kChunkBlock, 8) void k_jpeg_index_chunked(
     const long long* __restrict__ entry_off, rk_jpeg_entry* __restrict__ entries, long long n_entries, int S, int max_rounds,
     unsigned char* __restrict__ ws, long long ws_bytes, int* __restrict__ status, int* __restrict__ route) {
     __shared__ rk_jpeg_huff tabs[6];
-    __shared__ ChunkShared sh;
+    __shared__ rkjpeg::ChunkShared sh;
     const int i = blockIdx.x, t = threadIdx.x;
     const rk_jpeg_frame f = frames[i];
     rkjpeg::Geometry g;
@@ -370,21 +301,11 @@ __global__ __launch_bounds__(kChunkBlock, 8) void k_jpeg_index_chunked(
         if (t == 0) route[i] = 0;
         return;
     }
-    constexpr int kWords = sizeof(rk_jpeg_huff) / 4;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {                       // unrolled: f.dc[c] with a run-time c would put the record in scratch
-        if (c >= g.ncomp) break;
-        const unsigned* d = reinterpret_cast<const unsigned*>(htabs + f.dc[c]);
-        const unsigned* a = reinterpret_cast<const unsigned*>(htabs + f.ac[c]);
-        for (int k = t; k < kWords; k += kChunkBlock) {
-            reinterpret_cast<unsigned*>(&tabs[c])[k] = d[k];
-            reinterpret_cast<unsigned*>(&tabs[3 + c])[k] = a[k];
-        }
-    }
+    load_tables(f, g.ncomp, htabs, tabs, t, kChunkBlock);
     __syncthreads();
     WordSrc src{streams + f.stream_off, (uintptr_t)streams, (uintptr_t)(streams + stream_bytes), 0, 0ull};
-    const int rounds = chunked_frame(f, g, src, tabs, sh, reinterpret_cast<ChunkState*>(ws + ws_lo), nch, S, max_rounds, E,
-                                     entries + first);
+    const int rounds = chunked_frame(f, g, src, tabs, sh, reinterpret_cast<rkjpeg::ChunkState*>(ws + ws_lo), nch, S,
+                                     max_rounds, E, entries + first);
     if (t == 0) {
         route[i] = rounds;
         if (rounds) status[i] = RK_JPEG_OK;
@@ -444,12 +365,10 @@ __global__ __launch_bounds__(kWave) void k_jpeg_entropy_seg(const unsigned char*
     const int E = seg_mcus[p];
     const long long first = entry_off[p], last = entry_off[p + 1];
     if (!rkjpeg::index_row_ok(g, E, first, last, n_entries) || last - first > gridDim.y || s >= last - first) return;
-    load_tables(f, g.ncomp, htabs, tabs, lane);
+    load_tables(f, g.ncomp, htabs, tabs, lane, kWave);
     __syncthreads();
     WindowSrcT<kSegWindow> src{streams + f.stream_off, win, -(long long)kSegWindow - 1, f.stream_len, lane};
-    int zigzag = 0;
-    for (int k = 0; k < 64; ++k) zigzag = rkjpeg::natural_of(k) == lane ? k : zigzag;
-    LaneSink sink{reinterpret_cast<short*>(ws + reinterpret_cast<const long long*>(ws)[j]), lane, zigzag, 0};
+    LaneSink sink = lane_sink(ws, j, lane);
     const long long nmcu = (long long)g.mcux * g.mcuy, m_begin = (long long)s * E;
     const long long m_end = m_begin + E < nmcu ? m_begin + E : nmcu;
     const rk_jpeg_entry entry = entries[first + s];
@@ -541,6 +460,31 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_count(int* __restrict__ status,
     }
 }
 
+// What the entry points ask of their arguments, in their order: pointers, then counts, sizes and alignment, then the workspace.
+bool any_null(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (!p) return true;
+    return false;
+}
+bool counts_ok(std::initializer_list<int> counts) {         // grid dimensions and 16-bit table indices: 1 .. 65535
+    for (int v : counts)
+        if (v < 1 || v > 65535) return false;
+    return true;
+}
+bool sizes_ok(std::initializer_list<long long> sizes) {     // byte and entry counts
+    for (long long v : sizes)
+        if (v < 0) return false;
+    return true;
+}
+bool aligned(uintptr_t to, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & (to - 1)) return false;
+    return true;
+}
+bool workspace_ok(const void* workspace, size_t bytes, long long least) {
+    return workspace && aligned(16, {workspace}) && (long long)bytes >= least;
+}
+
 }  // namespace
 }  // namespace rk
 
@@ -557,12 +501,11 @@ int rk_jpeg_decode_u8(const unsigned char* streams, long long stream_bytes, cons
                       const unsigned short* qtabs, const rk_jpeg_huff* htabs, int nq, int nh, int n, unsigned char* rgb,
                       long long rgb_bytes, void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream) {
     using namespace rk;
-    if (!streams || !frames || !qtabs || !htabs || !rgb || !status) return RK_ERR_NULL_POINTER;
-    if (n < 1 || n > 65535 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || stream_bytes < 0 || rgb_bytes < 0)
+    if (any_null({streams, frames, qtabs, htabs, rgb, status})) return RK_ERR_NULL_POINTER;
+    if (!counts_ok({n, nq, nh}) || !sizes_ok({stream_bytes, rgb_bytes}) || !aligned(8, {frames}) || !aligned(4, {htabs, status}) ||
+        !aligned(2, {qtabs}))
         return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)qtabs & 1) || ((uintptr_t)status & 3)) return RK_ERR_BAD_DIMS;
-    if (!workspace || ((uintptr_t)workspace & 15) || (long long)workspace_bytes < rkjpeg::offset_table_bytes(n))
-        return RK_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, rkjpeg::offset_table_bytes(n))) return RK_ERR_WORKSPACE;
     const hipStream_t s = (hipStream_t)stream;
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     hipLaunchKernelGGL(k_jpeg_plan, dim3(1), dim3(kBlock), 0, s, frames, n, stream_bytes, rgb_bytes, nq, nh,
@@ -578,11 +521,9 @@ int rk_jpeg_build_index(const unsigned char* streams, long long stream_bytes, co
                         const rk_jpeg_huff* htabs, int nq, int nh, int n, const int* seg_mcus, const long long* entry_off,
                         rk_jpeg_entry* entries, long long n_entries, int* status, rk_stream_t stream) {
     using namespace rk;
-    if (!streams || !frames || !htabs || !seg_mcus || !entry_off || !entries || !status) return RK_ERR_NULL_POINTER;
-    if (n < 1 || n > 65535 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || stream_bytes < 0 || n_entries < 0)
-        return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)status & 3) || ((uintptr_t)seg_mcus & 3) ||
-        ((uintptr_t)entry_off & 7) || ((uintptr_t)entries & 7))
+    if (any_null({streams, frames, htabs, seg_mcus, entry_off, entries, status})) return RK_ERR_NULL_POINTER;
+    if (!counts_ok({n, nq, nh}) || !sizes_ok({stream_bytes, n_entries}) || !aligned(8, {frames, entry_off, entries}) ||
+        !aligned(4, {htabs, status, seg_mcus}))
         return RK_ERR_BAD_DIMS;
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_jpeg_index, dim3(n), dim3(kWave), 0, s, streams, stream_bytes, frames, htabs, nq, nh, seg_mcus,
@@ -604,15 +545,11 @@ int rk_jpeg_build_index_chunked(const unsigned char* streams, long long stream_b
                                 int max_rounds, void* workspace, size_t workspace_bytes, int* status, int* route,
                                 rk_stream_t stream) {
     using namespace rk;
-    if (!streams || !frames || !htabs || !seg_mcus || !entry_off || !entries || !status || !route) return RK_ERR_NULL_POINTER;
-    if (n < 1 || n > 65535 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || stream_bytes < 0 || n_entries < 0)
+    if (any_null({streams, frames, htabs, seg_mcus, entry_off, entries, status, route})) return RK_ERR_NULL_POINTER;
+    if (!counts_ok({n, nq, nh}) || !sizes_ok({stream_bytes, n_entries}) || !aligned(8, {frames, entry_off, entries}) ||
+        !aligned(4, {htabs, status, seg_mcus, route}) || !rkjpeg::chunk_bytes_ok(chunk_bytes) || max_rounds < 0 || max_rounds > 64)
         return RK_ERR_BAD_DIMS;
-    if (!rkjpeg::chunk_bytes_ok(chunk_bytes) || max_rounds < 0 || max_rounds > 64) return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)status & 3) || ((uintptr_t)seg_mcus & 3) ||
-        ((uintptr_t)entry_off & 7) || ((uintptr_t)entries & 7) || ((uintptr_t)route & 3))
-        return RK_ERR_BAD_DIMS;
-    if (!workspace || ((uintptr_t)workspace & 15) || (long long)workspace_bytes < rkjpeg::offset_table_bytes(n))
-        return RK_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, rkjpeg::offset_table_bytes(n))) return RK_ERR_WORKSPACE;
     const hipStream_t s = (hipStream_t)stream;
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     hipLaunchKernelGGL(k_jpeg_chunk_plan, dim3(1), dim3(kBlock), 0, s, frames, n, chunk_bytes, reinterpret_cast<long long*>(ws));
@@ -639,19 +576,14 @@ int rk_jpeg_decode_indexed_u8(const unsigned char* streams, long long stream_byt
                               int max_segments, unsigned char* rgb, long long rgb_bytes, void* workspace,
                               size_t workspace_bytes, int* status, rk_stream_t stream) {
     using namespace rk;
-    if (!streams || !frames || !qtabs || !htabs || !entries || !entry_off || !seg_mcus || !build_status || !pick || !rgb_off ||
-        !rgb || !status)
+    if (any_null({streams, frames, qtabs, htabs, entries, entry_off, seg_mcus, build_status, pick, rgb_off, rgb, status}))
         return RK_ERR_NULL_POINTER;
-    if (n < 1 || nq < 1 || nq > 65535 || nh < 1 || nh > 65535 || m < 1 || m > 65535 || max_segments < 1 || max_segments > 65535 ||
-        stream_bytes < 0 || rgb_bytes < 0 || n_entries < 0)
-        return RK_ERR_BAD_DIMS;
-    if (((uintptr_t)frames & 7) || ((uintptr_t)htabs & 3) || ((uintptr_t)qtabs & 1) || ((uintptr_t)status & 3) ||
-        ((uintptr_t)entries & 7) || ((uintptr_t)entry_off & 7) || ((uintptr_t)seg_mcus & 3) || ((uintptr_t)build_status & 3) ||
-        ((uintptr_t)pick & 3) || ((uintptr_t)rgb_off & 7))
+    if (n < 1 || !counts_ok({nq, nh, m, max_segments}) || !sizes_ok({stream_bytes, rgb_bytes, n_entries}) ||
+        !aligned(8, {frames, entries, entry_off, rgb_off}) || !aligned(4, {htabs, status, seg_mcus, build_status, pick}) ||
+        !aligned(2, {qtabs}))
         return RK_ERR_BAD_DIMS;
     const long long head = rkjpeg::indexed_head_bytes(m, max_segments);
-    if (!workspace || ((uintptr_t)workspace & 15) || (long long)workspace_bytes < head + rkjpeg::offset_table_bytes(m))
-        return RK_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, head + rkjpeg::offset_table_bytes(m))) return RK_ERR_WORKSPACE;
     const hipStream_t s = (hipStream_t)stream;
     unsigned char* base = static_cast<unsigned char*>(workspace);
     rk_jpeg_frame* gathered = reinterpret_cast<rk_jpeg_frame*>(base);

@@ -3,7 +3,9 @@
 // the walk that records those entries, and the same entries from many short walks in lock-step rounds -- jidctint's ISLOW
 // IDCT, fancy upsampling and YCbCr -> RGB.  The kernels only distribute this code over lanes; tests/jpeg_core_main.cpp,
 // tests/jpeg_index_main.cpp and tests/jpeg_chunked_main.cpp compile the same text for the CPU under AddressSanitizer /
-// UBSan, which is the bounds proof for the kernels' logic.
+// UBSan, which is the bounds proof for the kernels' logic.  That holds for everything in this file, the chunked build's
+// per-frame driver included: its phases are here, and what rk_jpeg.hip adds to them is barriers.  It does not hold for
+// what only rk_jpeg.hip has: the stream sources, the lane sink, the plan kernels' sums and the launch geometry.
 //
 // Every function is bounded by counts from the record and reads the stream through a source object that the caller
 // bounds; arithmetic that a hostile stream could overflow is done in unsigned (two's complement wrap, as the hardware).
@@ -86,7 +88,22 @@ RKJ_HD bool rgb_range_ok(const rk_jpeg_frame& f, long long rgb_bytes) {
     return f.rgb_off >= 0 && f.rgb_off <= rgb_bytes && need <= rgb_bytes - f.rgb_off;
 }
 
-// The record alone: RK_JPEG_OK or RK_JPEG_BAD_RECORD.  ws_begin / ws_end: the frame's region of the workspace.
+// A resident record (rk_jpeg_build_index) alone: RK_JPEG_OK or RK_JPEG_BAD_RECORD.  Its sizes, its segment and its
+// tables; not the output range and the workspace, which a resident frame gets only when it is picked.
+RKJ_HD int check_resident(const rk_jpeg_frame& f, long long stream_bytes, int nq, int nh) {
+    Geometry g;
+    if (!geometry(f, g)) return RK_JPEG_BAD_RECORD;
+    if (f.stream_off < 0 || f.stream_len < 0 || f.stream_off > stream_bytes || f.stream_len > stream_bytes - f.stream_off)
+        return RK_JPEG_BAD_RECORD;
+    if (f.restart_interval < 0 || f.restart_interval > 65535) return RK_JPEG_BAD_RECORD;
+    for (int c = 0; c < g.ncomp; ++c)
+        if (f.quant[c] >= nq || f.dc[c] >= nh || f.ac[c] >= nh) return RK_JPEG_BAD_RECORD;
+    return RK_JPEG_OK;
+}
+
+// A record that is decoded where it stands: check_resident's checks, the output range, and ws_end, the end of the frame's
+// region of the workspace.  Spelt out, not composed of check_resident: every composition tried gave k_jpeg_plan other
+// instructions than it had, and that kernel is in every decode launch (profiles/jpeg_refactor.txt).
 RKJ_HD int check_record(const rk_jpeg_frame& f, long long stream_bytes, long long rgb_bytes, int nq, int nh,
                         long long ws_end, long long workspace_bytes) {
     Geometry g;
@@ -98,19 +115,6 @@ RKJ_HD int check_record(const rk_jpeg_frame& f, long long stream_bytes, long lon
     for (int c = 0; c < g.ncomp; ++c)
         if (f.quant[c] >= nq || f.dc[c] >= nh || f.ac[c] >= nh) return RK_JPEG_BAD_RECORD;
     if (ws_end > workspace_bytes) return RK_JPEG_BAD_RECORD;
-    return RK_JPEG_OK;
-}
-
-// A resident record (rk_jpeg_build_index): check_record without the output range and the workspace, which a resident
-// frame gets only when it is picked.
-RKJ_HD int check_resident(const rk_jpeg_frame& f, long long stream_bytes, int nq, int nh) {
-    Geometry g;
-    if (!geometry(f, g)) return RK_JPEG_BAD_RECORD;
-    if (f.stream_off < 0 || f.stream_len < 0 || f.stream_off > stream_bytes || f.stream_len > stream_bytes - f.stream_off)
-        return RK_JPEG_BAD_RECORD;
-    if (f.restart_interval < 0 || f.restart_interval > 65535) return RK_JPEG_BAD_RECORD;
-    for (int c = 0; c < g.ncomp; ++c)
-        if (f.quant[c] >= nq || f.dc[c] >= nh || f.ac[c] >= nh) return RK_JPEG_BAD_RECORD;
     return RK_JPEG_OK;
 }
 
@@ -266,6 +270,52 @@ struct NoRecorder {
     RKJ_HD void at(long long, long long, int, int, int) {}
 };
 
+struct NullSink {
+    RKJ_HD void put(int, int) {}
+    RKJ_HD void end_block(long long) {}
+};
+
+// One block of component c, the only entropy block loop there is: the DC symbol and the predictor's update, the AC
+// symbols into sink.put, the overrun check (sink.end_block is the caller's); a refusal RETURNS its code from the function
+// that holds the block.  p0..p2 are the three predictors as scalars (a lane-private array indexed by c lives in scratch
+// memory); the DC difference is added in unsigned, so that a caller that lets the sums run (range false: they are sums of
+// differences, not predictors yet) wraps; range: the sum is the predictor and must stay inside +-2047, where the unsigned
+// sum is the signed one.
+// A macro, not a function, with its locals in the caller's scope (one use per scope): as a force-inlined function the
+// same text came out of the compiler with its blocks laid out otherwise, and the chain kernels, which are this loop
+// and little else, ran 5 % longer (profiles/jpeg_refactor.txt).  Expanded so, they are the instructions they were; its own
+// scope (do { } while (0)) changes them again, so it has none.
+#define RKJ_DECODE_BLOCK(range, br, tabs, c, p0, p1, p2, sink)                                          \
+    int s_ = huff_symbol((br), (tabs)[c]);                                                              \
+    if (s_ < 0) return RK_JPEG_BAD_CODE;                                                                \
+    if (s_ > 11) return RK_JPEG_BAD_VALUE;                                                              \
+    int dcv_ = (c) == 0 ? (p0) : ((c) == 1 ? (p1) : (p2));                                              \
+    if (s_) dcv_ = (int)((unsigned)dcv_ + (unsigned)receive_extend((br), s_));                          \
+    if ((range) && (dcv_ < -2047 || dcv_ > 2047)) return RK_JPEG_BAD_VALUE;                             \
+    (p0) = (c) == 0 ? dcv_ : (p0);                                                                      \
+    (p1) = (c) == 1 ? dcv_ : (p1);                                                                      \
+    (p2) = (c) == 2 ? dcv_ : (p2);                                                                      \
+    if (dcv_) (sink).put(0, dcv_);                                                                      \
+    int k_ = 1;                                                                                         \
+    for (int guard_ = 0; guard_ < 63 && k_ < 64; ++guard_) { /* at most 63 symbols a block */           \
+        const int rs_ = huff_symbol((br), (tabs)[3 + (c)]);                                             \
+        if (rs_ < 0) return RK_JPEG_BAD_CODE;                                                           \
+        const int r_ = rs_ >> 4;                                                                        \
+        s_ = rs_ & 15;                                                                                  \
+        if (s_ == 0) {                                                                                  \
+            if (r_ != 15) break; /* EOB */                                                              \
+            k_ += 16;            /* ZRL: a coefficient of this block must follow */                     \
+            if (k_ > 63) return RK_JPEG_BAD_RUN;                                                        \
+            continue;                                                                                   \
+        }                                                                                               \
+        k_ += r_;                                                                                       \
+        if (k_ > 63) return RK_JPEG_BAD_RUN;                                                            \
+        if (s_ > 10) return RK_JPEG_BAD_VALUE;                                                          \
+        (sink).put(k_, receive_extend((br), s_));                                                       \
+        ++k_;                                                                                           \
+    }                                                                                                   \
+    if ((br).overrun()) return RK_JPEG_TRUNCATED;
+
 RKJ_HD bool entry_equals(const rk_jpeg_entry& e, long long bit_pos, int p0, int p1, int p2) {
     return e.bit_pos == bit_pos && e.pred[0] == p0 && e.pred[1] == p1 && e.pred[2] == p2;
 }
@@ -314,35 +364,7 @@ RKJ_HD int walk_span(const rk_jpeg_frame& f, const Geometry& g, Src& src, const 
         }
         for (int j = 0; j < g.bpm; ++j, ++block) {
             const int c = j < nluma ? 0 : j - nluma + 1;
-            int s = huff_symbol(br, tabs[c]);
-            if (s < 0) return RK_JPEG_BAD_CODE;
-            if (s > 11) return RK_JPEG_BAD_VALUE;
-            int dcv = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
-            if (s) dcv += receive_extend(br, s);
-            if (dcv < -2047 || dcv > 2047) return RK_JPEG_BAD_VALUE;
-            pred0 = c == 0 ? dcv : pred0;
-            pred1 = c == 1 ? dcv : pred1;
-            pred2 = c == 2 ? dcv : pred2;
-            if (dcv) sink.put(0, dcv);
-            int k = 1;
-            for (int guard = 0; guard < 63 && k < 64; ++guard) {        // at most 63 symbols a block
-                const int rs = huff_symbol(br, tabs[3 + c]);
-                if (rs < 0) return RK_JPEG_BAD_CODE;
-                const int r = rs >> 4;
-                s = rs & 15;
-                if (s == 0) {
-                    if (r != 15) break;                                 // EOB
-                    k += 16;                                            // ZRL: a coefficient of this block must follow
-                    if (k > 63) return RK_JPEG_BAD_RUN;
-                    continue;
-                }
-                k += r;
-                if (k > 63) return RK_JPEG_BAD_RUN;
-                if (s > 10) return RK_JPEG_BAD_VALUE;
-                sink.put(k, receive_extend(br, s));
-                ++k;
-            }
-            if (br.overrun()) return RK_JPEG_TRUNCATED;
+            RKJ_DECODE_BLOCK(true, br, tabs, c, pred0, pred1, pred2, sink)
             sink.end_block(block);
         }
     }
@@ -373,10 +395,13 @@ RKJ_HD bool index_row_ok(const Geometry& g, int E, long long first, long long la
     return last - first == segment_count(g, E);
 }
 
-struct NullSink {
-    RKJ_HD void put(int, int) {}
-    RKJ_HD void end_block(long long) {}
-};
+RKJ_HD void write_entry(rk_jpeg_entry* e, long long bit_pos, int p0, int p1, int p2) {
+    e->bit_pos = bit_pos;
+    e->pred[0] = (short)p0;
+    e->pred[1] = (short)p1;
+    e->pred[2] = (short)p2;
+    e->reserved = 0;
+}
 
 // Writes the entry of every E-th MCU; `writer` says whether this caller stores (one lane of a wave that walks together).
 struct EntryRecorder {
@@ -386,13 +411,7 @@ struct EntryRecorder {
     bool writer;
     RKJ_HD void at(long long, long long bit_pos, int p0, int p1, int p2) {
         if (left == 0) {
-            if (writer) {
-                out->bit_pos = bit_pos;
-                out->pred[0] = (short)p0;
-                out->pred[1] = (short)p1;
-                out->pred[2] = (short)p2;
-                out->reserved = 0;
-            }
+            if (writer) write_entry(out, bit_pos, p0, p1, p2);
             ++out;
             left = E;
         }
@@ -439,40 +458,14 @@ struct ChunkSums {          // of one walk: MCUs completed, DC differences added
     int mcus, dc0, dc1, dc2;
 };
 
-// One MCU with nothing stored: every refusal of walk_span's loop body, in its order.  p0..p2 are running sums of the DC
-// differences; kRange: they are the true predictors and must stay inside +-2047.
+// One MCU with nothing stored: walk_span's loop body.  p0..p2 are running sums of the DC differences; kRange: they are
+// the true predictors and must stay inside +-2047.
 template <bool kRange, class Src>
 RKJ_HD int skip_mcu(BitReader<Src, true>& br, const Geometry& g, int nluma, const rk_jpeg_huff* tabs, int& p0, int& p1, int& p2) {
+    NullSink none;
     for (int j = 0; j < g.bpm; ++j) {
         const int c = j < nluma ? 0 : j - nluma + 1;
-        int s = huff_symbol(br, tabs[c]);
-        if (s < 0) return RK_JPEG_BAD_CODE;
-        if (s > 11) return RK_JPEG_BAD_VALUE;
-        int dcv = c == 0 ? p0 : (c == 1 ? p1 : p2);
-        if (s) dcv = (int)((unsigned)dcv + (unsigned)receive_extend(br, s));
-        if (kRange && (dcv < -2047 || dcv > 2047)) return RK_JPEG_BAD_VALUE;
-        p0 = c == 0 ? dcv : p0;
-        p1 = c == 1 ? dcv : p1;
-        p2 = c == 2 ? dcv : p2;
-        int k = 1;
-        for (int guard = 0; guard < 63 && k < 64; ++guard) {
-            const int rs = huff_symbol(br, tabs[3 + c]);
-            if (rs < 0) return RK_JPEG_BAD_CODE;
-            const int r = rs >> 4;
-            s = rs & 15;
-            if (s == 0) {
-                if (r != 15) break;
-                k += 16;
-                if (k > 63) return RK_JPEG_BAD_RUN;
-                continue;
-            }
-            k += r;
-            if (k > 63) return RK_JPEG_BAD_RUN;
-            if (s > 10) return RK_JPEG_BAD_VALUE;
-            (void)receive_extend(br, s);
-            ++k;
-        }
-        if (br.overrun()) return RK_JPEG_TRUNCATED;
+        RKJ_DECODE_BLOCK(kRange, br, tabs, c, p0, p1, p2, none)
     }
     return RK_JPEG_OK;
 }
@@ -532,12 +525,7 @@ RKJ_HD int index_chunk(const rk_jpeg_frame& f, const Geometry& g, Src& src, cons
         const long long pos = br.bit_pos();
         if (pos >= end_bit) return pos == expect_out ? RK_JPEG_OK : RK_JPEG_BAD_INDEX;
         if (until == 0) {
-            at->bit_pos = pos;
-            at->pred[0] = (short)p0;
-            at->pred[1] = (short)p1;
-            at->pred[2] = (short)p2;
-            at->reserved = 0;
-            ++at;
+            write_entry(at++, pos, p0, p1, p2);
             until = E;
         }
         --until;
@@ -551,6 +539,138 @@ RKJ_HD int index_chunk(const rk_jpeg_frame& f, const Geometry& g, Src& src, cons
     }
     return RK_JPEG_BAD_INDEX;
 }
+
+// The chunked build of one frame by `lanes` lanes (at most kChunkBlock), lane t taking chunks t, t + lanes, ...: the
+// PHASES below, each called by every lane with a barrier after it and none inside.  k_jpeg_index_chunked is that sequence
+// with __syncthreads() for the barriers, tests/jpeg_chunked_main.cpp runs each phase for t = 0 .. lanes - 1 in turn; no
+// phase reads what another lane writes in the same phase, so both compute the same.
+//
+//   chunk_init
+//   for r = 1 .. max_rounds:  chunk_walk_dirty;  chunk_advance(r);  leave with rounds = r where chunk_converged(r)
+//   (never converged: the frame is the sequential walk's)
+//   chunk_run_sums;  dead = chunk_sums_in_front;  chunk_final_pass(dead);  chunk_route(rounds)
+constexpr int kChunkBlock = 1024;
+
+struct ChunkState {         // 32 bytes of the workspace per chunk
+    ChunkSums sums;         // of the chunk's last walk; after chunk_sums_in_front: of all chunks in front of it
+    int pin, pout;          // bit positions (at most 8 * 512 * kMaxChunks); pout -1: the walk is dead
+    int dirty, reserved;    // p_in changed: the chunk is walked in the next round
+};
+static_assert(sizeof(ChunkState) == 32, "ChunkState is 32 bytes");
+
+struct ChunkShared {        // of one frame, shared by its lanes
+    int part[kChunkBlock][4], part_dead[kChunkBlock];
+    int changed[2], refused, finished;
+};
+
+RKJ_HD int chunk_min(int a, int b) { return a < b ? a : b; }
+
+RKJ_HD void chunk_init(int t, int lanes, ChunkShared& sh, ChunkState* __restrict__ st, int nch, int S) {
+    for (int c = t; c < nch; c += lanes) {
+        st[c].pin = 8 * c * S;
+        st[c].dirty = 1;
+    }
+    if (t == 0) sh.changed[0] = sh.changed[1] = sh.refused = sh.finished = 0;
+}
+
+template <class Src>
+RKJ_HD void chunk_walk_dirty(int t, int lanes, const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs,
+                             ChunkState* __restrict__ st, int nch, int S) {
+    for (int c = t; c < nch; c += lanes) {
+        if (!st[c].dirty) continue;
+        st[c].dirty = 0;
+        ChunkSums own;
+        st[c].pout = (int)walk_chunk(f, g, src, tabs, st[c].pin, 8LL * (c + 1) * S, own);
+        st[c].sums = own;
+    }
+}
+
+// Jacobi: every p_in comes from the round just walked.  This round's flag is changed[r & 1]; the other one, which every
+// lane read before it came through the barrier in front of this phase, is cleared for the next round.
+RKJ_HD void chunk_advance(int t, int lanes, ChunkShared& sh, ChunkState* __restrict__ st, int nch, int S, int r) {
+    if (t == 0) sh.changed[(r + 1) & 1] = 0;
+    for (int c = t; c < nch; c += lanes) {
+        const int want = (int)chunk_next_in(c, S, c ? st[c - 1].pout : 0);
+        if (want != st[c].pin) {
+            st[c].pin = want;
+            st[c].dirty = 1;
+            sh.changed[r & 1] = 1;
+        }
+    }
+}
+RKJ_HD bool chunk_converged(const ChunkShared& sh, int r) { return !sh.changed[r & 1]; }    // the same word for every lane
+
+// The sums in front of every chunk, in two levels: each lane a run of `per` consecutive chunks, then the lanes' totals.
+RKJ_HD void chunk_run(int t, int lanes, int nch, int& per, int& lo, int& hi) {
+    per = (nch + lanes - 1) / lanes;
+    lo = chunk_min(nch, t * per);
+    hi = chunk_min(nch, lo + per);
+}
+
+RKJ_HD void chunk_run_sums(int t, int lanes, ChunkShared& sh, const ChunkState* __restrict__ st, int nch) {
+    int per, lo, hi;
+    chunk_run(t, lanes, nch, per, lo, hi);
+    unsigned a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    int dead = nch;
+    for (int c = hi - 1; c >= lo; --c) {
+        const ChunkSums own = st[c].sums;
+        a0 += (unsigned)own.mcus;
+        a1 += (unsigned)own.dc0;
+        a2 += (unsigned)own.dc1;
+        a3 += (unsigned)own.dc2;
+        if (st[c].pout < 0) dead = c;
+    }
+    sh.part[t][0] = (int)a0;
+    sh.part[t][1] = (int)a1;
+    sh.part[t][2] = (int)a2;
+    sh.part[t][3] = (int)a3;
+    sh.part_dead[t] = dead;
+}
+
+// st[c].sums becomes what the chunks in front of c add up to.  -> the first dead walk (nch: none): the sums in front
+// of the chunks up to it are true.
+RKJ_HD int chunk_sums_in_front(int t, int lanes, const ChunkShared& sh, ChunkState* __restrict__ st, int nch) {
+    int per, lo, hi;
+    chunk_run(t, lanes, nch, per, lo, hi);
+    unsigned a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    int dead = nch;
+    const int used = chunk_min(lanes, (nch + per - 1) / per);      // the lanes whose runs are not empty
+    for (int k = 0; k < used; ++k) {
+        if (k < t) {
+            a0 += (unsigned)sh.part[k][0];
+            a1 += (unsigned)sh.part[k][1];
+            a2 += (unsigned)sh.part[k][2];
+            a3 += (unsigned)sh.part[k][3];
+        }
+        dead = chunk_min(dead, sh.part_dead[k]);
+    }
+    for (int c = lo; c < hi; ++c) {
+        const ChunkSums own = st[c].sums;
+        st[c].sums = ChunkSums{(int)a0, (int)a1, (int)a2, (int)a3};
+        a0 += (unsigned)own.mcus;
+        a1 += (unsigned)own.dc0;
+        a2 += (unsigned)own.dc1;
+        a3 += (unsigned)own.dc2;
+    }
+    return dead;
+}
+
+template <class Src>
+RKJ_HD void chunk_final_pass(int t, int lanes, const rk_jpeg_frame& f, const Geometry& g, Src& src, const rk_jpeg_huff* tabs,
+                             ChunkShared& sh, const ChunkState* __restrict__ st, int nch, int S, int E,
+                             rk_jpeg_entry* __restrict__ row, int dead) {
+    for (int c = t; c < nch && c <= dead; c += lanes) {
+        const bool last = c + 1 == nch;
+        const ChunkSums before = st[c].sums;
+        bool done = false;
+        const int rc = index_chunk(f, g, src, tabs, st[c].pin, last ? f.stream_len * 8 + 1 : 8LL * (c + 1) * S,
+                                   last ? -1LL : (long long)st[c].pout, before, E, row, &done);
+        if (rc != RK_JPEG_OK) sh.refused = 1;
+        if (done) sh.finished = 1;
+    }
+}
+// -> the rounds after which the walk had converged, 0 where the frame is left to the sequential walk.
+RKJ_HD int chunk_route(const ChunkShared& sh, int rounds) { return sh.finished && !sh.refused ? rounds : 0; }
 
 // ------------------------------------------------------------------------------------------------ IDCT
 // libjpeg's jidctint.c (jpeg_idct_islow), 8-bit samples: CONST_BITS 13, PASS1_BITS 2, dequantisation by multiplication,
@@ -701,5 +821,7 @@ RKJ_HD void pixel_rgb(const unsigned char* base, const Geometry& g, int x, int y
     }
     ycc_to_rgb(luma, chroma_at(base + g.plane_off[1], g, x, y), chroma_at(base + g.plane_off[2], g, x, y), rgb);
 }
+
+#undef RKJ_DECODE_BLOCK
 
 }  // namespace rkjpeg

@@ -507,8 +507,7 @@ class FrameLoader(_Feeder):
         nj = int(packed.layout[0])
         rows = None
         if nj and self.entropy == "rows":                   # the batch's index tables travel behind the host-decoded frames
-            (host_frames, _, _, _), _ = jpeg.sections(packed.blob, packed.layout)
-            rows = jpeg.row_tables(np.frombuffer(host_frames.numpy(), dtype=jpeg.FRAME_DTYPE), self.chunk_bytes)
+            rows = jpeg.row_tables(jpeg.records(packed.blob, packed.layout), self.chunk_bytes)
             rows_at = nbytes = (nbytes + 15) & ~15
             nbytes += rows.tables.numel()
         if self._copied[slot] is not None:
@@ -718,8 +717,7 @@ class DeviceFrameCache(_Feeder):
         self._fallback = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
         for frame, at in zip(res.fallback, self._fallback_off):
             self._fallback[at:at + frame.numel()].copy_(frame.reshape(-1))
-        (frames, _, _, _), _ = jpeg.sections(res.blob, res.layout)
-        self._host_frames = np.frombuffer(frames.numpy().tobytes(), dtype=jpeg.FRAME_DTYPE)
+        self._host_frames = jpeg.records(res.blob, res.layout).copy()
         self._frame_ws = jpeg.frame_workspace_bytes(self._host_frames)
         self._rgb = self._ws = self._status = None
         self._errors = torch.zeros((), dtype=torch.int64, device=self.device)

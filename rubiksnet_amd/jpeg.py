@@ -229,20 +229,59 @@ def huffman_record(counts, values):
     return rec
 
 
+def _align16(v):
+    return (v + 15) & ~15
+
+
+def _geometry(frames):
+    """rkjpeg::geometry of a FRAME_DTYPE array, in numpy -> (ok, mcux, mcuy, bytes), each per record: are its sizes
+    valid, its MCUs per row and per column (1 where they are not), the bytes of its region of the workspace (0 where
+    they are not: 128 of coefficients and 64 of samples per block, rounded up to 16)."""
+    f = np.asarray(frames).reshape(-1)
+    w, h, nc, s = (f[k].astype(np.int64) for k in ("width", "height", "components", "sampling"))
+    ok = (w >= 1) & (w <= MAX_SIDE) & (h >= 1) & (h <= MAX_SIDE) & ((nc == 1) | ((nc == 3) & (s >= 0) & (s <= 2)))
+    hs, vs = np.where((nc == 3) & (s >= 1), 2, 1), np.where((nc == 3) & (s == 2), 2, 1)
+    mcux = np.where(ok, (w + 8 * hs - 1) // (8 * hs), 1)
+    mcuy = np.where(ok, (h + 8 * vs - 1) // (8 * vs), 1)
+    blocks = mcux * mcuy * np.where(nc == 1, 1, hs * vs + 2)
+    return ok, mcux, mcuy, np.where(ok, _align16(blocks * 192), 0)
+
+
+def _mcus(width, height, components, sampling):
+    """(MCUs per row, MCUs per column) of one frame's sizes, by _geometry."""
+    rec = np.array([(0, 0, 0, width, height, components, sampling, 0, 0, 0, 0, 0)], dtype=FRAME_DTYPE)
+    return tuple(int(v[0]) for v in _geometry(rec)[1:3])
+
+
+def frame_workspace_bytes(frames):
+    """int64 per record of a FRAME_DTYPE array: the bytes of its region of the workspace (0 for sizes that are not valid),
+    what workspace_bytes_for sums (a resident set asks once and indexes the answer per batch)."""
+    return _geometry(frames)[3]
+
+
 def workspace_bytes_for(frames):
     """rk_jpeg_workspace_bytes of a FRAME_DTYPE array, in numpy (a DataLoader worker does not load the HIP library)."""
-    frames = np.asarray(frames)
-    total = ((frames.size + 1) * 8 + 15) & ~15
-    for f in frames.reshape(-1):
-        w, h, nc, s = int(f["width"]), int(f["height"]), int(f["components"]), int(f["sampling"])
-        if not (1 <= w <= MAX_SIDE and 1 <= h <= MAX_SIDE) or nc not in (1, 3) or (nc == 3 and not 0 <= s <= 2):
-            continue
-        hs, vs = (2 if nc == 3 and s >= 1 else 1), (2 if nc == 3 and s == 2 else 1)
-        mx, my = (w + 8 * hs - 1) // (8 * hs), (h + 8 * vs - 1) // (8 * vs)
-        blocks = mx * my * (1 if nc == 1 else hs * vs + 2)
-        planes = mx * my * 64 * (1 if nc == 1 else hs * vs + 2)
-        total += (blocks * 128 + planes + 15) & ~15
-    return total
+    per_frame = frame_workspace_bytes(frames)
+    return _align16((per_frame.size + 1) * 8) + int(per_frame.sum())
+
+
+def sections(blob, layout):
+    """(frames, htabs, qtabs, streams) views of a PackedJpeg blob (host or device) and (n, nh, nq)."""
+    n, nh, nq, o_frames, o_huff, o_quant, o_stream, stream_bytes = (int(v) for v in layout.tolist())
+    return (blob[o_frames:o_frames + n * 64], blob[o_huff:o_huff + nh * HUFF_DTYPE.itemsize],
+            blob[o_quant:o_quant + nq * 128], blob[o_stream:o_stream + stream_bytes]), (n, nh, nq)
+
+
+def records(blob, layout):
+    """The frame records of a host blob as a FRAME_DTYPE array: a view, an edit lands in the blob."""
+    return np.frombuffer(sections(blob, layout)[0][0].numpy(), dtype=FRAME_DTYPE)
+
+
+def _check_tensors(specs, say=str):
+    """specs: (name, tensor, dtype); say: how the message names a dtype."""
+    for name, t, dt in specs:
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor on the GPU" % (name, say(dt)))
 
 
 # ------------------------------------------------------------------------------------------------- collate
@@ -261,10 +300,6 @@ def _host_rgb(item):
     from PIL import Image
     with Image.open(io.BytesIO(item)) as im:
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
-
-
-def _align16(v):
-    return (v + 15) & ~15
 
 
 def pack_jpeg_clips(samples):
@@ -348,10 +383,9 @@ def launch_decode(streams, frames, qtabs, htabs, n, rgb, workspace, status, nq=N
     uint8 [n * 64] (rk_jpeg_frame records), qtabs uint8 [nq * 128], htabs uint8 [nh * 1424], rgb uint8 [rgb_bytes],
     workspace uint8 (16-byte aligned), status int32 [n + 1].  Nothing is allocated and the host does not wait."""
     from . import _native
-    for name, t in (("streams", streams), ("frames", frames), ("qtabs", qtabs), ("htabs", htabs), ("rgb", rgb),
-                    ("workspace", workspace)):
-        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous uint8 tensor on the GPU" % name)
+    _check_tensors(((name, t, torch.uint8) for name, t in (("streams", streams), ("frames", frames), ("qtabs", qtabs),
+                                                           ("htabs", htabs), ("rgb", rgb), ("workspace", workspace))),
+                   say=lambda dt: "uint8")
     if status.dtype != torch.int32 or not status.is_cuda or status.numel() < n + 1 or not status.is_contiguous():
         raise ValueError("status must be int32 [n + 1] on the GPU")
     if frames.numel() < n * FRAME_DTYPE.itemsize:
@@ -383,11 +417,6 @@ ResidentJpeg = collections.namedtuple("ResidentJpeg", [
 ])
 
 
-def _mcus(width, height, components, sampling):
-    hs, vs = (2 if components == 3 and sampling >= 1 else 1), (2 if components == 3 and sampling == 2 else 1)
-    return (width + 8 * hs - 1) // (8 * hs), (height + 8 * vs - 1) // (8 * vs)
-
-
 def pack_resident(videos, seg_mcus=None):
     """A set of videos for rk_jpeg_build_index / rk_jpeg_decode_indexed_u8.  videos: [(frames, label)] as pack_jpeg_clips
     takes them (a frame: the bytes of its file, or uint8 [H, W, 3]); all frames of a video share one size (ValueError
@@ -396,8 +425,8 @@ def pack_resident(videos, seg_mcus=None):
     resident frame gets its place when it is picked) and the index tables.  Files parse_jpeg refuses are decoded here,
     once, and stay RGB."""
     packed = pack_jpeg_clips(videos)
-    (frames, _, _, _), (n, _, _) = sections(packed.blob, packed.layout)
-    rec = np.frombuffer(frames.numpy(), dtype=FRAME_DTYPE)                  # a view: the edits land in the blob
+    rec = records(packed.blob, packed.layout)
+    n = rec.size
     host = {int(off): i for i, (off, _) in enumerate(packed.fallback)}
     rows, slots, r = [], [], 0
     for off, h, w, k in packed.clips.tolist():
@@ -411,9 +440,7 @@ def pack_resident(videos, seg_mcus=None):
                 r += 1
     assert r == n
     rec["rgb_off"][:] = 0
-    mcux, mcuy = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-    for i, f in enumerate(rec):
-        mcux[i], mcuy[i] = _mcus(int(f["width"]), int(f["height"]), int(f["components"]), int(f["sampling"]))
+    _, mcux, mcuy, _ = _geometry(rec)
     E = mcux.copy() if seg_mcus is None else np.broadcast_to(np.asarray(seg_mcus, dtype=np.int64), (n,)).copy()
     if n and (E.min() < 1 or E.max() >= 1 << 31):
         raise ValueError("seg_mcus must be at least 1")
@@ -461,11 +488,9 @@ def launch_build_index_chunked(streams, frames, htabs, nq, nh, n, seg_mcus, entr
     8-byte aligned), workspace (16-byte aligned) uint8; seg_mcus int32 [n], entry_off int64 [n + 1], status int32 [n + 1],
     route int32 [n].  Nothing is allocated and the host does not wait."""
     from . import _native
-    for name, t, dt in (("streams", streams, torch.uint8), ("frames", frames, torch.uint8), ("htabs", htabs, torch.uint8),
-                        ("entries", entries, torch.uint8), ("workspace", workspace, torch.uint8), ("seg_mcus", seg_mcus, torch.int32),
-                        ("entry_off", entry_off, torch.int64), ("status", status, torch.int32), ("route", route, torch.int32)):
-        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor on the GPU" % (name, dt))
+    _check_tensors((("streams", streams, torch.uint8), ("frames", frames, torch.uint8), ("htabs", htabs, torch.uint8),
+                    ("entries", entries, torch.uint8), ("workspace", workspace, torch.uint8), ("seg_mcus", seg_mcus, torch.int32),
+                    ("entry_off", entry_off, torch.int64), ("status", status, torch.int32), ("route", route, torch.int32)))
     _check_chunking(chunk_bytes, max_rounds)
     if frames.numel() < n * 64 or seg_mcus.numel() < n or entry_off.numel() < n + 1 or status.numel() < n + 1 or route.numel() < n:
         raise ValueError("frames, seg_mcus, entry_off, status or route is shorter than n = %d asks for" % n)
@@ -498,8 +523,7 @@ def build_index(resident, device="cuda:0", method="chain", chunk_bytes=256, max_
     status = torch.zeros(n + 1, dtype=torch.int32, device=device)
     route = torch.zeros(n, dtype=torch.int32, device=device) if method == "chunked" else None
     if method == "chunked":
-        (host_frames, _, _, _), _ = sections(resident.blob, resident.layout)
-        rec = np.frombuffer(host_frames.numpy(), dtype=FRAME_DTYPE)
+        rec = records(resident.blob, resident.layout)
     for lo in range(0, n, MAX_LAUNCH):
         k = min(MAX_LAUNCH, n - lo)
         part = torch.zeros(k + 1, dtype=torch.int32, device=device)
@@ -561,17 +585,6 @@ def _head_bytes(m, max_segments):
     return m * 64 + ((m * max_segments * 4 + 15) & ~15)
 
 
-def frame_workspace_bytes(frames):
-    """int64 per record of a FRAME_DTYPE array: the bytes of its region of the workspace (0 for sizes that are not valid),
-    what workspace_bytes_for sums, without a Python loop (a resident set asks once and indexes the answer per batch)."""
-    f = np.asarray(frames).reshape(-1)
-    w, h, nc, s = (f[k].astype(np.int64) for k in ("width", "height", "components", "sampling"))
-    ok = (w >= 1) & (w <= MAX_SIDE) & (h >= 1) & (h <= MAX_SIDE) & ((nc == 1) | ((nc == 3) & (s >= 0) & (s <= 2)))
-    hs, vs = np.where((nc == 3) & (s >= 1), 2, 1), np.where((nc == 3) & (s == 2), 2, 1)
-    blocks = ((w + 8 * hs - 1) // (8 * hs)) * ((h + 8 * vs - 1) // (8 * vs)) * np.where(nc == 1, 1, hs * vs + 2)
-    return np.where(ok, (blocks * 192 + 15) & ~15, 0)
-
-
 def indexed_workspace_bytes_for(frames, pick, max_segments, per_frame=None):
     """rk_jpeg_indexed_workspace_bytes of a FRAME_DTYPE array and a pick list, in numpy.  per_frame: frame_workspace_bytes
     of `frames`, where the caller keeps it."""
@@ -589,10 +602,8 @@ def launch_decode_indexed(index, pick, rgb_off, max_segments, rgb, workspace, st
     host does not wait."""
     from . import _native
     m = pick.numel()
-    for name, t, dt in (("pick", pick, torch.int32), ("rgb_off", rgb_off, torch.int64), ("rgb", rgb, torch.uint8),
-                        ("workspace", workspace, torch.uint8), ("status", status, torch.int32)):
-        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor on the GPU" % (name, dt))
+    _check_tensors((("pick", pick, torch.int32), ("rgb_off", rgb_off, torch.int64), ("rgb", rgb, torch.uint8),
+                    ("workspace", workspace, torch.uint8), ("status", status, torch.int32)))
     if rgb_off.numel() != m or status.numel() < m + 1:
         raise ValueError("pick [%d], rgb_off [%d], status [%d]: want m, m, m + 1" % (m, rgb_off.numel(), status.numel()))
     _native.launch("rk_jpeg_decode_indexed_u8", rgb.device, index.streams.data_ptr(), index.streams.numel(),
@@ -600,13 +611,6 @@ def launch_decode_indexed(index, pick, rgb_off, max_segments, rgb, workspace, st
                    index.entries.data_ptr(), index.n_entries, index.entry_off.data_ptr(), index.seg_mcus.data_ptr(),
                    index.status.data_ptr(), pick.data_ptr(), rgb_off.data_ptr(), m, int(max_segments), rgb.data_ptr(),
                    rgb.numel(), workspace.data_ptr(), workspace.numel(), status.data_ptr())
-
-
-def sections(blob, layout):
-    """(frames, htabs, qtabs, streams) views of a PackedJpeg blob (host or device) and (n, nh, nq)."""
-    n, nh, nq, o_frames, o_huff, o_quant, o_stream, stream_bytes = (int(v) for v in layout.tolist())
-    return (blob[o_frames:o_frames + n * 64], blob[o_huff:o_huff + nh * HUFF_DTYPE.itemsize],
-            blob[o_quant:o_quant + nq * 128], blob[o_stream:o_stream + stream_bytes]), (n, nh, nq)
 
 
 # ------------------------------------------------------------------------------------------------- a streamed batch by rows
@@ -626,11 +630,7 @@ def row_tables(frames, chunk_bytes=256):
     sizes are not valid gets one segment of one MCU; the build refuses it from its fields."""
     f = np.asarray(frames).reshape(-1)
     n = f.size
-    w, h, nc, s = (f[k].astype(np.int64) for k in ("width", "height", "components", "sampling"))
-    ok = (w >= 1) & (w <= MAX_SIDE) & (h >= 1) & (h <= MAX_SIDE) & ((nc == 1) | ((nc == 3) & (s >= 0) & (s <= 2)))
-    hs, vs = np.where((nc == 3) & (s >= 1), 2, 1), np.where((nc == 3) & (s == 2), 2, 1)
-    mcux = np.where(ok, (w + 8 * hs - 1) // (8 * hs), 1)
-    mcuy = np.where(ok, (h + 8 * vs - 1) // (8 * vs), 1)
+    _, mcux, mcuy, per_frame = _geometry(f)
     entry_off = np.concatenate([[0], np.cumsum(mcuy)]).astype(np.int64)
     parts = (mcux.astype(np.int32), entry_off, np.arange(n, dtype=np.int32), f["rgb_off"].astype(np.int64))
     offsets, at = [], 0
@@ -642,7 +642,7 @@ def row_tables(frames, chunk_bytes=256):
         tables[off:off + part.nbytes] = part.view(np.uint8)
     most = int(mcuy.max())
     return RowTables(torch.from_numpy(tables), tuple(offsets), n, int(entry_off[-1]), most,
-                     chunked_workspace_bytes_for(f, chunk_bytes), indexed_workspace_bytes_for(f, parts[2], most))
+                     chunked_workspace_bytes_for(f, chunk_bytes), indexed_workspace_bytes_for(f, parts[2], most, per_frame))
 
 
 def launch_decode_rows(streams, frames, qtabs, htabs, nq, nh, rows, tables, entries, build_ws, build_status, route, rgb,
@@ -687,8 +687,7 @@ def decode_jpeg_frames(packed, device="cuda:0", out=None, workspace=None, entrop
         raise ValueError("out holds %d bytes, the batch decodes to %d" % (rgb.numel(), packed.rgb_bytes))
     status = torch.zeros(n + 1, dtype=torch.int32, device=device)
     if n and entropy == "rows":
-        (host_frames, _, _, _), _ = sections(packed.blob, packed.layout)
-        rows = row_tables(np.frombuffer(host_frames.numpy(), dtype=FRAME_DTYPE), chunk_bytes)
+        rows = row_tables(records(packed.blob, packed.layout), chunk_bytes)
         if workspace is None:
             workspace = torch.empty(rows.decode_bytes, dtype=torch.uint8, device=device)
         elif workspace.numel() < rows.decode_bytes:

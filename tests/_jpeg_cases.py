@@ -1,11 +1,31 @@
-"""What tests/test_jpeg.py and tests/test_jpeg_gpu.py share: the committed JPEG fixtures (tests/golden/jpeg_cases.npz,
-written by tests/golden/gen_jpeg_golden.py) read once."""
+"""What the JPEG tests share: the committed JPEG fixtures (tests/golden/jpeg_cases.npz, written by
+tests/golden/gen_jpeg_golden.py) read once, and the build of the host programs tests/jpeg_*_main.cpp."""
 import functools
 import os
+import shutil
+import subprocess
 
 import numpy as np
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def build_program(name, directory):
+    """tests/<name>.cpp + tests/jpeg_host.hpp + csrc/rk_jpeg_core.hpp with the host compiler, AddressSanitizer + UBSan: a
+    stand-alone program -> its path, None without a compiler."""
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        return None
+    exe = os.path.join(str(directory), name)
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rubiksnet_amd", "csrc"),
+           os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe]
+    # the sanitizer runtimes inside the program (g++ links them as shared libraries unless told otherwise): the program
+    # then runs as it is, whatever else the process environment loads
+    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
+        subprocess.check_call(cmd)
+    return exe
 
 
 @functools.lru_cache(maxsize=None)

@@ -5,7 +5,6 @@ tests/jpeg_chunked_main.cpp (csrc/rk_jpeg_core.hpp under AddressSanitizer + UBSa
 import functools
 import io
 import os
-import shutil
 import subprocess
 import tempfile
 
@@ -15,7 +14,6 @@ import _jpeg_cases as jc
 import _jpeg_index_cases as ic
 from rubiksnet_amd import jpeg
 
-ROOT = ic.ROOT
 SETTINGS = [(16, 64), (64, 16), (256, 64), (16, 8), (256, 0), (256, 1)]         # chunk_bytes, max_rounds
 NOISE = ["noise_q100_444", "noise_q100_std_444"]
 SHORT = ["flat_420", "b8_444", "n4x3_420"]                                      # shorter than one 256-byte chunk
@@ -60,8 +58,9 @@ def resident():
 
 
 def records(res):
-    (frames, _, _, _), _ = jpeg.sections(res.blob, res.layout)
-    return np.frombuffer(frames.numpy().tobytes(), dtype=jpeg.FRAME_DTYPE)
+    rec = jpeg.records(res.blob, res.layout).copy()
+    rec.flags.writeable = False                 # the set is cached: nobody edits it through this
+    return rec
 
 
 def chunk_counts(rec, chunk_bytes):
@@ -71,28 +70,13 @@ def chunk_counts(rec, chunk_bytes):
     return np.where(ok, (length + chunk_bytes - 1) // chunk_bytes, 0)
 
 
-def build_program(directory):
-    """tests/jpeg_chunked_main.cpp with the host compiler, AddressSanitizer + UBSan, exactly as
-    _jpeg_index_cases.build_program builds its program; None without a compiler."""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        return None
-    exe = os.path.join(directory, "jpeg_chunked_main")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rubiksnet_amd", "csrc"),
-           os.path.join(ROOT, "tests", "jpeg_chunked_main.cpp"), "-o", exe]
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    return exe
-
-
 @functools.lru_cache(maxsize=None)
 def host_run():
     """One run of the host program over resident() at every setting.  None without a compiler; otherwise a dict: names,
     chain int32 [n] and chain_entries (the sequential walk), and per setting (chunk_bytes, max_rounds) a dict of status,
     route, passed, chunks int32 [n] and entries.  The program must end with status 0 and no sanitizer report."""
     with tempfile.TemporaryDirectory() as tmp:
-        exe = build_program(tmp)
+        exe = jc.build_program("jpeg_chunked_main", tmp)
         if exe is None:
             return None
         names, res = resident()

@@ -4,7 +4,6 @@ per process of the host program tests/jpeg_index_main.cpp (csrc/rk_jpeg_core.hpp
 stand-alone child process) over all of it."""
 import functools
 import os
-import shutil
 import subprocess
 import tempfile
 
@@ -13,7 +12,6 @@ import numpy as np
 import _jpeg_cases as jc
 from rubiksnet_amd import jpeg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # 2x2 MCUs; 3x3; 4:4:4; grayscale; R = 1; RSTn wrapping past 7; 5x3 MCUs with R = 2 (row entries on and between restarts)
 CASES = ["p17x23_420", "p33x17_422", "p17x23_444", "p17x23_gray", "rst1_48x48_420", "rst1_64x48_420", "rst2_40x24_444"]
 KINDS = ("bit + 1", "bit - 1", "bit_pos = 8 len + 1", "bit_pos = -1", "pred + 1", "pred = 4000", "swapped")
@@ -64,25 +62,9 @@ def tampers():
 
 def rgb_table(res):
     """Back-to-back places for every record -> (int64 rgb_off [n], rgb_bytes)."""
-    (frames, _, _, _), _ = jpeg.sections(res.blob, res.layout)
-    rec = np.frombuffer(frames.numpy().tobytes(), dtype=jpeg.FRAME_DTYPE)
+    rec = jpeg.records(res.blob, res.layout).copy()
     sizes = rec["width"].astype(np.int64) * rec["height"] * 3
     return np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64), int(sizes.sum())
-
-
-def build_program(directory):
-    """tests/jpeg_index_main.cpp with the host compiler, AddressSanitizer + UBSan, exactly as test_jpeg.py's core_main
-    builds its program; None without a compiler."""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
-        return None
-    exe = os.path.join(directory, "jpeg_index_main")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rubiksnet_amd", "csrc"),
-           os.path.join(ROOT, "tests", "jpeg_index_main.cpp"), "-o", exe]
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    return exe
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,12 +73,12 @@ def host_run():
     whole / built / tiled int32 [n], entries (ENTRY_DTYPE [n_entries]), tampered int32 [t, 2], rgb uint8 [rgb_bytes],
     rgb_off int64 [n], stderr.  The program must end with status 0 and no sanitizer report."""
     with tempfile.TemporaryDirectory() as tmp:
-        exe = build_program(tmp)
+        exe = jc.build_program("jpeg_index_main", tmp)
         if exe is None:
             return None
         names, res = resident()
         (frames, htabs, qtabs, streams), (n, nh, nq) = jpeg.sections(res.blob, res.layout)
-        rec = np.frombuffer(frames.numpy().tobytes(), dtype=jpeg.FRAME_DTYPE).copy()
+        rec = jpeg.records(res.blob, res.layout).copy()
         rgb_off, rgb_bytes = rgb_table(res)
         rec["rgb_off"] = rgb_off
         tam = np.asarray(tampers(), dtype=np.int32).reshape(-1, 4)

@@ -1,6 +1,6 @@
 // Host run of the chunked index build of the device JPEG decode (rubiksnet_amd/csrc/rk_jpeg_core.hpp): what
-// rk_jpeg_build_index_chunked does per frame, with the lanes of its workgroup simulated in order and the rounds in
-// lock-step, beside the sequential walk (record_index) on the same frames, on exactly-sized heap buffers.
+// rk_jpeg_build_index_chunked does per frame -- the kernel's own phases, its lanes taken in order between the barriers --
+// beside the sequential walk (record_index) on the same frames, on exactly-sized heap buffers.
 // tests/test_jpeg_chunked.py builds this with -fsanitize=address,undefined: the bounds proof for the kernel's logic, and
 // the oracle for its route array.
 //
@@ -13,33 +13,11 @@
 //        converged), passed [n] (chunks of the fixed point that only passed a position through), chunks [n] (the frame's
 //        chunk count, 0 where it cannot take the chunked route), entries [n_entries * 16]
 // Entries no walk wrote keep the byte 0x5A.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <memory>
-#include <vector>
-
-#include "rk_jpeg_core.hpp"
+#include "jpeg_host.hpp"
 
 namespace {
 
-constexpr int kLanes = 1024;
-
-struct PtrSrc {
-    const unsigned char* p;
-    int byte(long long pos) { return p[pos]; }
-};
-
-template <class T>
-std::unique_ptr<T[]> read_exact(FILE* fh, size_t count) {       // exactly `count` elements: ASan sees the true end
-    std::unique_ptr<T[]> buf(new T[count ? count : 1]);
-    if (count && fread(buf.get(), sizeof(T), count, fh) != count) {
-        fprintf(stderr, "short read\n");
-        exit(2);
-    }
-    return buf;
-}
+constexpr int kLanes = rkjpeg::kChunkBlock;
 
 struct Frame {
     rk_jpeg_frame f;
@@ -49,75 +27,48 @@ struct Frame {
     int E;
 };
 
-// The chunked route of one frame, as the kernel's workgroup takes it -> rounds (> 0: `row` holds the frame's entries and
-// its code is 0) or 0 (the frame is the sequential walk's).
+template <class Phase>
+void every_lane(Phase phase) {
+    for (int t = 0; t < kLanes; ++t) phase(t);
+}
+
+// The chunked route of one frame: the phases the kernel's workgroup runs (rk_jpeg_core.hpp), each for every lane in turn
+// where the kernel has a barrier, on exactly nch chunk states -> rounds (> 0: `row` holds the frame's entries and its
+// code is 0) or 0 (the frame is the sequential walk's).
 int chunked(const Frame& fr, int S, int max_rounds, rk_jpeg_entry* row, int* passed) {
-    const int nch = rkjpeg::chunk_count(fr.f, S);
+    using namespace rkjpeg;
+    const int nch = chunk_count(fr.f, S);
     *passed = 0;
     if (nch < 1 || max_rounds < 1) return 0;
-    std::vector<long long> pin((size_t)nch), pout((size_t)nch);
-    std::vector<unsigned char> dirty((size_t)nch, 1);
-    std::vector<rkjpeg::ChunkSums> sums((size_t)nch);
+    std::unique_ptr<ChunkState[]> st(new ChunkState[nch]);
+    std::unique_ptr<ChunkShared> sh(new ChunkShared);
+    std::vector<int> dead((size_t)kLanes);      // a lane-local of the kernel that lives across a barrier
     PtrSrc src{fr.stream.get()};
-    for (int c = 0; c < nch; ++c) pin[c] = 8LL * c * S;
+    every_lane([&](int t) { chunk_init(t, kLanes, *sh, st.get(), nch, S); });
     int rounds = 0;
     for (int r = 1; r <= max_rounds && !rounds; ++r) {
-        for (int t = 0; t < kLanes; ++t)
-            for (int c = t; c < nch; c += kLanes)
-                if (dirty[c]) {
-                    dirty[c] = 0;
-                    pout[c] = rkjpeg::walk_chunk(fr.f, fr.g, src, fr.tabs, pin[c], 8LL * (c + 1) * S, sums[c]);
-                }
-        bool changed = false;                   // every lane reads this round's results only: the order does not matter
-        for (int t = 0; t < kLanes; ++t)
-            for (int c = t; c < nch; c += kLanes) {
-                const long long want = rkjpeg::chunk_next_in(c, S, c ? pout[c - 1] : 0);
-                if (want != pin[c]) {
-                    pin[c] = want;
-                    dirty[c] = 1;
-                    changed = true;
-                }
-            }
-        if (!changed) rounds = r;
+        every_lane([&](int t) { chunk_walk_dirty(t, kLanes, fr.f, fr.g, src, fr.tabs, st.get(), nch, S); });
+        every_lane([&](int t) { chunk_advance(t, kLanes, *sh, st.get(), nch, S, r); });
+        if (chunk_converged(*sh, r)) rounds = r;
     }
     if (!rounds) return 0;
-    int dead = nch;                             // the first dead walk: the sums in front of the chunks up to it are true
-    for (int c = nch - 1; c >= 0; --c)
-        if (pout[c] < 0) dead = c;
-    rkjpeg::ChunkSums run = {0, 0, 0, 0};
-    for (int c = 0; c < nch; ++c) {
-        const rkjpeg::ChunkSums own = sums[c];
-        sums[c] = run;
-        run.mcus = (int)((unsigned)run.mcus + (unsigned)own.mcus);
-        run.dc0 = (int)((unsigned)run.dc0 + (unsigned)own.dc0);
-        run.dc1 = (int)((unsigned)run.dc1 + (unsigned)own.dc1);
-        run.dc2 = (int)((unsigned)run.dc2 + (unsigned)own.dc2);
-    }
-    bool refused = false, finished = false;
-    for (int t = 0; t < kLanes; ++t)
-        for (int c = t; c < nch; c += kLanes) {
-            if (c > dead) continue;
-            const bool last = c + 1 == nch;
-            const long long end_bit = last ? fr.f.stream_len * 8 + 1 : 8LL * (c + 1) * S;
-            if (pin[c] >= end_bit) ++*passed;
-            bool done = false;
-            if (rkjpeg::index_chunk(fr.f, fr.g, src, fr.tabs, pin[c], end_bit, last ? -1 : pout[c], sums[c], fr.E, row,
-                                    &done) != RK_JPEG_OK)
-                refused = true;
-            finished = finished || done;
-        }
-    return finished && !refused ? rounds : 0;
+    every_lane([&](int t) { chunk_run_sums(t, kLanes, *sh, st.get(), nch); });
+    every_lane([&](int t) { dead[t] = chunk_sums_in_front(t, kLanes, *sh, st.get(), nch); });
+    every_lane([&](int t) {
+        chunk_final_pass(t, kLanes, fr.f, fr.g, src, fr.tabs, *sh, st.get(), nch, S, fr.E, row, dead[t]);
+    });
+    for (int c = 0; c < nch && c <= dead[0]; ++c)
+        *passed += st[c].pin >= (c + 1 == nch ? fr.f.stream_len * 8 + 1 : 8LL * (c + 1) * S);
+    return chunk_route(*sh, rounds);
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* fh = fopen(argv[1], "rb");
-    if (!fh) return 2;
     int head[4];
     long long sizes[4];
-    if (fread(head, sizeof head, 1, fh) != 1 || fread(sizes, sizeof sizes, 1, fh) != 1) return 2;
+    FILE* fh = open_in(argc, argv, head, sizes);
+    if (!fh) return 2;
     const int n = head[0], nq = head[1], nh = head[2], nset = head[3];
     const long long stream_bytes = sizes[0], n_entries = sizes[1];
     if (n < 1 || nq < 1 || nh < 1 || nset < 0 || stream_bytes < 0 || n_entries < 0) return 2;
@@ -144,10 +95,7 @@ int main(int argc, char** argv) {
             record[i] = chain[i] = RK_JPEG_BAD_INDEX;
             continue;
         }
-        for (int c = 0; c < 3; ++c) {
-            fr.tabs[c] = htabs[fr.f.dc[c < fr.g.ncomp ? c : 0]];
-            fr.tabs[3 + c] = htabs[fr.f.ac[c < fr.g.ncomp ? c : 0]];
-        }
+        copy_tables(fr.f, fr.g.ncomp, htabs.get(), fr.tabs);
         fr.stream.reset(new unsigned char[fr.f.stream_len ? fr.f.stream_len : 1]);
         memcpy(fr.stream.get(), streams.get() + fr.f.stream_off, (size_t)fr.f.stream_len);
         PtrSrc src{fr.stream.get()};

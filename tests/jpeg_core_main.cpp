@@ -7,51 +7,13 @@
 //   IN : int32 n, nq, nh, 0; int64 stream_bytes, rgb_bytes, workspace_bytes, 0; frames [n * 64]; htabs [nh * 1424];
 //        qtabs [nq * 128]; streams [stream_bytes]
 //   OUT: int32 status [n + 1]; rgb [rgb_bytes] (bytes no frame owns keep 0xA5)
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <memory>
-#include <vector>
-
-#include "rk_jpeg_core.hpp"
-
-namespace {
-
-struct PtrSrc {
-    const unsigned char* p;
-    int byte(long long pos) { return p[pos]; }
-};
-
-struct BlockSink {
-    short* coefs;
-    short block[64];
-    void put(int k, int v) { block[rkjpeg::natural_of(k)] = (short)v; }
-    void end_block(long long b) {
-        memcpy(coefs + b * 64, block, sizeof block);
-        memset(block, 0, sizeof block);
-    }
-};
-
-template <class T>
-std::unique_ptr<T[]> read_exact(FILE* fh, size_t count) {       // exactly `count` elements: ASan sees the true end
-    std::unique_ptr<T[]> buf(new T[count ? count : 1]);
-    if (count && fread(buf.get(), sizeof(T), count, fh) != count) {
-        fprintf(stderr, "short read\n");
-        exit(2);
-    }
-    return buf;
-}
-
-}  // namespace
+#include "jpeg_host.hpp"
 
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* fh = fopen(argv[1], "rb");
-    if (!fh) return 2;
     int head[4];
     long long sizes[4];
-    if (fread(head, sizeof head, 1, fh) != 1 || fread(sizes, sizeof sizes, 1, fh) != 1) return 2;
+    FILE* fh = open_in(argc, argv, head, sizes);
+    if (!fh) return 2;
     const int n = head[0], nq = head[1], nh = head[2];
     const long long stream_bytes = sizes[0], rgb_bytes = sizes[1], workspace_bytes = sizes[2];
     if (n < 1 || nq < 1 || nh < 1 || stream_bytes < 0 || rgb_bytes < 0 || workspace_bytes < rkjpeg::offset_table_bytes(n)) return 2;
@@ -83,31 +45,17 @@ int main(int argc, char** argv) {
         if (status[i] == RK_JPEG_OK) {      // k_jpeg_entropy
             rkjpeg::geometry(f, g);
             rk_jpeg_huff tabs[6];
-            for (int c = 0; c < 3; ++c) {
-                tabs[c] = htabs[f.dc[c < g.ncomp ? c : 0]];
-                tabs[3 + c] = htabs[f.ac[c < g.ncomp ? c : 0]];
-            }
+            copy_tables(f, g.ncomp, htabs.get(), tabs);
             PtrSrc src{streams.get() + f.stream_off};
             BlockSink sink{reinterpret_cast<short*>(base), {0}};
             status[i] = rkjpeg::decode_scan(f, g, src, tabs, sink);
         }
-        if (status[i] == RK_JPEG_OK) {      // k_jpeg_idct
-            for (long long b = 0; b < g.nblocks; ++b) {
-                int comp, stride;
-                long long off;
-                rkjpeg::block_place(g, b, &comp, &off, &stride);
-                rkjpeg::idct_islow(reinterpret_cast<const short*>(base) + b * 64, qtabs.get() + (long long)f.quant[comp] * 64,
-                                   base + g.plane_off[comp] + off, stride);
-            }
-        }
-        if (rkjpeg::rgb_range_ok(f, rgb_bytes)) {       // k_jpeg_colour
+        if (rkjpeg::rgb_range_ok(f, rgb_bytes)) {       // k_jpeg_idct, k_jpeg_colour; a failed frame is zeroed
             unsigned char* out = rgb.get() + f.rgb_off;
-            const int npix = f.width * f.height;
-            if (status[i] != RK_JPEG_OK) {
-                memset(out, 0, 3 * (size_t)npix);
-            } else {
-                for (int p = 0; p < npix; ++p) rkjpeg::pixel_rgb(base, g, p % f.width, p / f.width, out + 3LL * p);
-            }
+            if (status[i] == RK_JPEG_OK)
+                region_to_rgb(f, g, qtabs.get(), base, out);
+            else
+                memset(out, 0, 3 * (size_t)f.width * f.height);
         }
         status[n] += status[i] != RK_JPEG_OK;          // k_jpeg_count
     }

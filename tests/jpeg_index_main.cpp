@@ -14,43 +14,11 @@
 //        coefficients (a failed frame is zeroed; bytes no frame owns keep 0xA5)
 // Tamper kinds: 0 bit_pos + 1, 1 bit_pos - 1, 2 bit_pos = 8 * stream_len + 1, 3 bit_pos = -1, 4 pred[0] + 1,
 // 5 pred[0] = 4000, 6 entries a and b swapped.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <memory>
-#include <vector>
-
-#include "rk_jpeg_core.hpp"
+#include "jpeg_host.hpp"
 
 namespace {
 
-struct PtrSrc {
-    const unsigned char* p;
-    int byte(long long pos) { return p[pos]; }
-};
-
-struct BlockSink {
-    short* coefs;
-    short block[64];
-    void put(int k, int v) { block[rkjpeg::natural_of(k)] = (short)v; }
-    void end_block(long long b) {
-        memcpy(coefs + b * 64, block, sizeof block);
-        memset(block, 0, sizeof block);
-    }
-};
-
 constexpr short kUntouched = 0x7F7F;
-
-template <class T>
-std::unique_ptr<T[]> read_exact(FILE* fh, size_t count) {       // exactly `count` elements: ASan sees the true end
-    std::unique_ptr<T[]> buf(new T[count ? count : 1]);
-    if (count && fread(buf.get(), sizeof(T), count, fh) != count) {
-        fprintf(stderr, "short read\n");
-        exit(2);
-    }
-    return buf;
-}
 
 struct Frame {
     rk_jpeg_frame f;
@@ -92,29 +60,18 @@ int by_segments(const Frame& fr, const rk_jpeg_entry* entries, std::vector<short
 }
 
 void to_rgb(const Frame& fr, const std::vector<short>& coefs, const unsigned short* qtabs, unsigned char* out) {
-    const rkjpeg::Geometry& g = fr.g;
-    std::vector<unsigned char> region((size_t)g.bytes, 0);
-    memcpy(region.data(), coefs.data(), (size_t)g.coef_bytes);
-    for (long long b = 0; b < g.nblocks; ++b) {
-        int comp, stride;
-        long long off;
-        rkjpeg::block_place(g, b, &comp, &off, &stride);
-        rkjpeg::idct_islow(reinterpret_cast<const short*>(region.data()) + b * 64, qtabs + (long long)fr.f.quant[comp] * 64,
-                           region.data() + g.plane_off[comp] + off, stride);
-    }
-    const int npix = fr.f.width * fr.f.height;
-    for (int p = 0; p < npix; ++p) rkjpeg::pixel_rgb(region.data(), g, p % fr.f.width, p / fr.f.width, out + 3LL * p);
+    std::vector<unsigned char> region((size_t)fr.g.bytes, 0);
+    memcpy(region.data(), coefs.data(), (size_t)fr.g.coef_bytes);
+    region_to_rgb(fr.f, fr.g, qtabs, region.data(), out);
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* fh = fopen(argv[1], "rb");
-    if (!fh) return 2;
     int head[4];
     long long sizes[4];
-    if (fread(head, sizeof head, 1, fh) != 1 || fread(sizes, sizeof sizes, 1, fh) != 1) return 2;
+    FILE* fh = open_in(argc, argv, head, sizes);
+    if (!fh) return 2;
     const int n = head[0], nq = head[1], nh = head[2], ntamper = head[3];
     const long long stream_bytes = sizes[0], rgb_bytes = sizes[1], n_entries = sizes[2];
     if (n < 1 || nq < 1 || nh < 1 || ntamper < 0 || stream_bytes < 0 || rgb_bytes < 0 || n_entries < 0) return 2;
@@ -144,10 +101,7 @@ int main(int argc, char** argv) {
         fr.nmcu = (long long)fr.g.mcux * fr.g.mcuy;
         if (!rkjpeg::index_row_ok(fr.g, fr.E, entry_off[i], entry_off[i + 1], n_entries)) return 2;
         fr.nseg = entry_off[i + 1] - entry_off[i];
-        for (int c = 0; c < 3; ++c) {
-            fr.tabs[c] = htabs[fr.f.dc[c < fr.g.ncomp ? c : 0]];
-            fr.tabs[3 + c] = htabs[fr.f.ac[c < fr.g.ncomp ? c : 0]];
-        }
+        copy_tables(fr.f, fr.g.ncomp, htabs.get(), fr.tabs);
         fr.stream = streams.get() + fr.f.stream_off;
         rk_jpeg_entry* mine = entries.get() + entry_off[i];
 

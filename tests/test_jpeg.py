@@ -5,7 +5,6 @@ bit-equal on every golden and failing cleanly on every corrupted file.  No GPU."
 import hashlib
 import io
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,7 +14,6 @@ import torch
 import _jpeg_cases as jc
 from rubiksnet_amd import jpeg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL_GOOD = jc.SUPPORTED + jc.CLIP
 
 
@@ -182,17 +180,9 @@ def test_workspace_bytes_equal_the_library(tmp_path):
 @pytest.fixture(scope="module")
 def core_main(tmp_path_factory):
     """tests/jpeg_core_main.cpp + csrc/rk_jpeg_core.hpp, host compiler, AddressSanitizer + UBSan; a stand-alone program."""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
+    exe = jc.build_program("jpeg_core_main", tmp_path_factory.mktemp("jpeg_core"))
+    if exe is None:
         pytest.skip("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("jpeg_core") / "jpeg_core_main")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rubiksnet_amd", "csrc"),
-           os.path.join(ROOT, "tests", "jpeg_core_main.cpp"), "-o", exe]
-    # the sanitizer runtimes inside the program (g++ links them as shared libraries unless told otherwise): the program
-    # then runs as it is, whatever else the process environment loads
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
     return exe
 
 
