@@ -854,6 +854,70 @@ int rk_jpeg_decode_indexed_u8(const unsigned char* streams, long long stream_byt
                               int max_segments, unsigned char* rgb, long long rgb_bytes, void* workspace,
                               size_t workspace_bytes, int* status, rk_stream_t stream);
 
+/* ---- resident frames kept as packed DCT coefficients (rk_jpeg.hip) ----
+ * A resident set is read again every epoch, but its Huffman code needs undoing once.  What the entropy stage leaves --
+ * short[64] per block, natural order, not dequantised -- is kept without its zeros, and a batch is decoded from that:
+ * no Huffman stage, the same IDCT on the same coefficients, the same RGB bit for bit.
+ * One frame's REGION of the blob (every part on a 2-byte boundary, little endian):
+ *   uint32 off[nblocks]   byte offset of block b's record from the region's start; blocks in scan order (MCU by MCU, in
+ *                         an MCU the luma blocks row by row, then Cb, then Cr), MCU padding blocks included
+ *   the records, back to back in block order: off[0] = 4 * nblocks, record b + 1 starts where record b ends, the last
+ *   one ends the region
+ *   record: uint64 header   bit 0: the AC values are 16-bit; bit k (1..63): the AC coefficient at zigzag position k is
+ *                           not zero
+ *           int16  DC
+ *           the non-zero AC values in zigzag order, int8 each where all of them fit, else int16 each, padded with a
+ *           zero byte to an even count: 10 + n * w rounded up to even, 10 .. 136 bytes
+ * Building (a set is processed in slabs of frames, so that the 128-byte-per-block workspace stays bounded):
+ * rk_jpeg_coef_sizes runs the entropy stage ONCE over the slab's n records -- entries == NULL: rk_jpeg_decode_u8's one
+ * chain per frame; otherwise rk_jpeg_decode_indexed_u8's one chain per segment by the given scan index (entries,
+ * n_entries, entry_off, seg_mcus, build_status, max_segments as documented there; rk_jpeg_build_index_chunked makes
+ * them) -- and then measures what it left:
+ *   workspace    device, 16-byte aligned, rk_jpeg_indexed_workspace_bytes(frames, n, {0 .. n - 1}, n, max_segments)
+ *                bytes (max_segments 1 where entries == NULL); it holds the coefficients until rk_jpeg_coef_pack
+ *   status       device int [n + 1]: the frame's code as the decoders give it, [n] the count of non-zero codes; a
+ *                frame whose blocks do not fit block_cap is RK_JPEG_BAD_RECORD
+ *   first_block  device long long [n + 1]: the exclusive sum of the frames' block counts (written)
+ *   block_off    device unsigned [block_cap]: at first_block[i] + b the offset of block b's record in frame i's region
+ *   region_off   device long long [n + 1]: the exclusive sum of the frames' region lengths, [n] the total; a frame
+ *                with a non-zero code has a region of length 0
+ * rk_jpeg_coef_pack then writes the offset table and the records of every frame with code 0 to blob + region_off[i]
+ * (the caller allocates region_off[n] bytes -- or more and shifts region_off -- between the two calls, which is why
+ * they are two); the same frames, workspace, max_segments, status, block_off and first_block.  A region that does not
+ * lie inside [0, blob_bytes) on a 2-byte boundary with exactly the measured length is not written.
+ * rk_jpeg_decode_coef_u8 decodes frames pick[j] (device int [m]) of a set of n packed frames to rgb + rgb_off[j]:
+ *   blob         device bytes, 2-byte aligned      region_off   device long long [n + 1], absolute in blob
+ *   frames       device [n] records; stream_off, stream_len, rgb_off and the Huffman indices are not used
+ *   build_status device int [n]: the codes rk_jpeg_coef_sizes gave; a frame with a non-zero code is not read, gets
+ *                that code and goes out as a zero frame
+ *   workspace    device, 16-byte aligned, rk_jpeg_coef_workspace_bytes(frames, n, pick, m): the m gathered records, a
+ *                flag per picked frame, an offset table and the component planes -- no coefficient is stored: a lane
+ *                expands one block's record straight into the IDCT
+ * The blob and the tables are untrusted device data.  RK_JPEG_BAD_RECORD as for rk_jpeg_decode_indexed_u8 (a pick
+ * outside [0, n), sizes, the output range, a quantisation index >= nq, the workspace).  RK_JPEG_BAD_INDEX, and a zero
+ * frame, before anything outside the frame's region is read: a region that is not inside the blob, not on a 2-byte
+ * boundary or not between 14 and 140 bytes per block long; an offset that is odd, inside the table or less than 10
+ * bytes from the region's end; off[0] != 4 * nblocks; a header that says 16-bit values and no value; a record whose
+ * length, from its header, does not end exactly where the next record starts (the region, for the last).  Every loop
+ * is bounded by the block count and the 63 positions of a header.  Six launches on `stream`, a linear chain: no
+ * allocation, no host wait, no atomics (lanes that refuse a block store the same flag); capturable.  m in [1, 65535].
+ * rk_jpeg_coef_sizes and rk_jpeg_coef_pack: n, nq, nh, max_segments in [1, 65535]; they enqueue only.  Return codes as
+ * rk_jpeg_decode_indexed_u8.  rk_jpeg_coef_workspace_bytes: from HOST copies; 0 for a NULL table, n < 1 or m < 1; a pick
+ * outside [0, n) takes no planes.                                                                                     */
+int rk_jpeg_coef_sizes(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                       const rk_jpeg_huff* htabs, int nq, int nh, int n, const rk_jpeg_entry* entries, long long n_entries,
+                       const long long* entry_off, const int* seg_mcus, const int* build_status, int max_segments,
+                       void* workspace, size_t workspace_bytes, int* status, unsigned* block_off, long long block_cap,
+                       long long* first_block, long long* region_off, rk_stream_t stream);
+int rk_jpeg_coef_pack(const rk_jpeg_frame* frames, int n, int max_segments, const void* workspace, size_t workspace_bytes,
+                      const int* status, const unsigned* block_off, long long block_cap, const long long* first_block,
+                      const long long* region_off, unsigned char* blob, long long blob_bytes, rk_stream_t stream);
+size_t rk_jpeg_coef_workspace_bytes(const rk_jpeg_frame* frames_host, int n, const int* pick_host, int m);
+int rk_jpeg_decode_coef_u8(const unsigned char* blob, long long blob_bytes, const rk_jpeg_frame* frames,
+                           const unsigned short* qtabs, int nq, int n, const long long* region_off, const int* build_status,
+                           const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
+                           void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream);
+
 /* ---- squeeze-and-excitation gate of RubiksNet-Small -- widening row f3 of SURVEY 8(f) --------------
  * SELayer (rubiksnet/backbone.py:56-71): y = x * sigmoid(W2 relu(W1 mean_hw(x))).  x, y, dy, dx [F, C, P];
  * mean / gate / dgate [F, C] f32.  squeeze: mean over P; scale: y = x * gate; scale_backward: dx = dy * gate and

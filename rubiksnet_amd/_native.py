@@ -177,6 +177,17 @@ SIGNATURES["rk_jpeg_build_index_chunked"] = (_i, [_p, ctypes.c_longlong, _p, _p,
 SIGNATURES["rk_jpeg_indexed_workspace_bytes"] = (_sz, [_p, _i, _p, _i, _i])
 SIGNATURES["rk_jpeg_decode_indexed_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _p, ctypes.c_longlong, _p, _p, _p, _p,
                                                 _p, _i, _i, _p, ctypes.c_longlong, _p, _sz, _p, _p])
+# resident frames as packed coefficients: streams, stream_bytes, frames, htabs, nq, nh, n, entries, n_entries, entry_off, seg_mcus,
+# build_status, max_segments, workspace, workspace_bytes, status, block_off, block_cap, first_block, region_off, stream / frames,
+# n, max_segments, workspace, workspace_bytes, status, block_off, block_cap, first_block, region_off, blob, blob_bytes, stream /
+# host frame table, n, host pick, m -> bytes / blob, blob_bytes, frames, qtabs, nq, n, region_off, build_status, pick, rgb_off, m,
+# rgb, rgb_bytes, workspace, workspace_bytes, status, stream
+SIGNATURES["rk_jpeg_coef_sizes"] = (_i, [_p, ctypes.c_longlong, _p, _p, _i, _i, _i, _p, ctypes.c_longlong, _p, _p, _p, _i, _p, _sz, _p,
+                                         _p, ctypes.c_longlong, _p, _p, _p])
+SIGNATURES["rk_jpeg_coef_pack"] = (_i, [_p, _i, _i, _p, _sz, _p, _p, ctypes.c_longlong, _p, _p, _p, ctypes.c_longlong, _p])
+SIGNATURES["rk_jpeg_coef_workspace_bytes"] = (_sz, [_p, _i, _p, _i])
+SIGNATURES["rk_jpeg_decode_coef_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, ctypes.c_longlong, _p, _sz,
+                                             _p, _p])
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw

@@ -460,6 +460,241 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_count(int* __restrict__ status,
     }
 }
 
+// ---------------------------------------------------------------------------------------------- packed coefficients
+// rk_jpeg_coef_sizes / rk_jpeg_coef_pack / rk_jpeg_decode_coef_u8 (the format and its checks: rk_jpeg_core.hpp).
+//
+//   building, after the entropy stage of a slab (k_jpeg_plan + k_jpeg_entropy, or + k_jpeg_entropy_seg + k_jpeg_seg_status):
+//   k_coef_blocks        one workgroup: the exclusive sum of the frames' block counts; a frame past block_cap is refused
+//   k_coef_block_sizes   a lane per block: the header of its 64 coefficients -> the bytes of its record
+//   k_coef_frame_scan    a workgroup per frame: those bytes -> each record's offset in the frame's region, the region's length
+//   k_coef_region_scan   one workgroup: the lengths -> the regions' offsets
+//   k_coef_pack          a lane per block: the table entry and the record
+//
+//   per batch
+//   k_jpeg_gather, k_coef_plan (records and regions checked, the planes laid out), k_coef_idct, k_coef_status,
+//   k_jpeg_colour, k_jpeg_count
+//
+// k_coef_idct is a lane per block, as k_jpeg_idct: the lane reads its two table entries, its header and then only the
+// values the header names -- reads of its own length per lane.  Lanes next to each other hold blocks next to each other,
+// whose records lie back to back, so a wave's reads fall into a few consecutive cache lines (a record is 10 .. 136
+// bytes, some 20 .. 40 for video frames) and are served from L2 after the first touch; the three dependent reads
+// (offset, header, values) are the whole chain, where the Huffman stage has one per symbol.  Staging a workgroup's
+// records in LDS first would make the global reads whole lines, but the bytes are few (the packed set is read at a
+// small fraction of what HBM gives) and a lane's LDS reads would be as scattered as its global ones.  The expansion is
+// unrolled over the 63 positions with constant indices, so the block stays in registers and goes into idct_islow as
+// k_jpeg_idct's does.
+struct RegionSrc {          // a region of the blob, 2-byte aligned
+    const unsigned char* p;
+    __device__ __forceinline__ unsigned u16(long long at) const { return *reinterpret_cast<const unsigned short*>(p + at); }
+    __device__ __forceinline__ int s8(long long at) const { return *reinterpret_cast<const signed char*>(p + at); }
+};
+struct RegionDst {
+    unsigned char* p;
+    __device__ __forceinline__ void put16(long long at, unsigned v) { *reinterpret_cast<unsigned short*>(p + at) = (unsigned short)v; }
+    __device__ __forceinline__ void put8(long long at, int v) { p[at] = (unsigned char)v; }
+};
+
+__device__ __forceinline__ long long frame_blocks(const rk_jpeg_frame& f) {
+    rkjpeg::Geometry g;
+    return rkjpeg::geometry(f, g) ? g.nblocks : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_coef_blocks(const rk_jpeg_frame* __restrict__ frames, int n, long long block_cap,
+                                                        long long* __restrict__ first_block, int* __restrict__ status) {
+    __shared__ long long part[kBlock];
+    const int t = threadIdx.x, per = (n + kBlock - 1) / kBlock;
+    const int lo = min(n, t * per), hi = min(n, lo + per);
+    long long sum = 0;
+    for (int i = lo; i < hi; ++i) sum += frame_blocks(frames[i]);
+    part[t] = sum;
+    __syncthreads();
+    long long at = 0;
+    for (int k = 0; k < t; ++k) at += part[k];
+    for (int i = lo; i < hi; ++i) {
+        first_block[i] = at;
+        at += frame_blocks(frames[i]);
+        if (at > block_cap && status[i] == RK_JPEG_OK) status[i] = RK_JPEG_BAD_RECORD;
+    }
+    if (t == kBlock - 1) first_block[n] = at;
+}
+
+// The block's 64 coefficients out of the frame's coefficient region, as k_jpeg_idct reads them.
+__device__ __forceinline__ void load_block(const unsigned char* __restrict__ base, long long b, short* coef) {
+    const uint4* src = reinterpret_cast<const uint4*>(base + b * 128);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) reinterpret_cast<uint4*>(coef)[k] = src[k];
+}
+
+__global__ __launch_bounds__(kBlock) void k_coef_block_sizes(const rk_jpeg_frame* __restrict__ frames,
+                                                             const unsigned char* __restrict__ ws, const int* __restrict__ status,
+                                                             const long long* __restrict__ first_block,
+                                                             unsigned* __restrict__ block_off) {
+    const int i = blockIdx.x;
+    if (status[i] != RK_JPEG_OK) return;
+    rkjpeg::Geometry g;
+    rkjpeg::geometry(frames[i], g);
+    const unsigned char* base = ws + reinterpret_cast<const long long*>(ws)[i];
+    unsigned* out = block_off + first_block[i];
+    for (long long b = (long long)blockIdx.y * kBlock + threadIdx.x; b < g.nblocks; b += (long long)kBlock * gridDim.y) {
+        alignas(16) short coef[64];
+        load_block(base, b, coef);
+        out[b] = (unsigned)rkjpeg::coef_record_bytes(rkjpeg::coef_header_of(coef));
+    }
+}
+
+// In place: the records' bytes of frame i become their offsets in the region (behind the table); region_off[i] = the
+// region's length, 0 for a frame with a code.  At most 12.6 M blocks of 136 bytes: below 2^32.
+__global__ __launch_bounds__(kBlock) void k_coef_frame_scan(const rk_jpeg_frame* __restrict__ frames, const int* __restrict__ status,
+                                                            const long long* __restrict__ first_block,
+                                                            unsigned* __restrict__ block_off, long long* __restrict__ region_off) {
+    __shared__ long long part[kBlock];
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (status[i] != RK_JPEG_OK) {                      // uniform
+        if (t == 0) region_off[i] = 0;
+        return;
+    }
+    rkjpeg::Geometry g;
+    rkjpeg::geometry(frames[i], g);
+    unsigned* mine = block_off + first_block[i];
+    const long long per = (g.nblocks + kBlock - 1) / kBlock;
+    const long long lo = min(g.nblocks, t * per), hi = min(g.nblocks, lo + per);
+    long long sum = 0;
+    for (long long b = lo; b < hi; ++b) sum += mine[b];
+    part[t] = sum;
+    __syncthreads();
+    long long at = rkjpeg::coef_table_bytes(g);
+    for (int k = 0; k < t; ++k) at += part[k];
+    for (long long b = lo; b < hi; ++b) {
+        const unsigned bytes = mine[b];
+        mine[b] = (unsigned)at;
+        at += bytes;
+    }
+    if (t == kBlock - 1) region_off[i] = at;
+}
+
+// In place: region_off[0 .. n) from lengths to offsets, region_off[n] = the total.
+__global__ __launch_bounds__(kBlock) void k_coef_region_scan(long long* __restrict__ region_off, int n) {
+    __shared__ long long part[kBlock];
+    const int t = threadIdx.x, per = (n + kBlock - 1) / kBlock;
+    const int lo = min(n, t * per), hi = min(n, lo + per);
+    long long sum = 0;
+    for (int i = lo; i < hi; ++i) sum += region_off[i];
+    part[t] = sum;
+    __syncthreads();                                    // every length is read before any offset is written
+    long long at = 0;
+    for (int k = 0; k < t; ++k) at += part[k];
+    for (int i = lo; i < hi; ++i) {
+        const long long len = region_off[i];
+        region_off[i] = at;
+        at += len;
+    }
+    if (t == kBlock - 1) region_off[n] = at;
+}
+
+__global__ __launch_bounds__(kBlock) void k_coef_pack(const rk_jpeg_frame* __restrict__ frames, const unsigned char* __restrict__ ws,
+                                                      const int* __restrict__ status, const unsigned* __restrict__ block_off,
+                                                      long long block_cap, const long long* __restrict__ first_block,
+                                                      const long long* __restrict__ region_off, unsigned char* __restrict__ blob,
+                                                      long long blob_bytes) {
+    const int i = blockIdx.x;
+    if (status[i] != RK_JPEG_OK) return;
+    rkjpeg::Geometry g;
+    rkjpeg::geometry(frames[i], g);
+    const long long lo = region_off[i], hi = region_off[i + 1], fb = first_block[i];
+    if (!rkjpeg::coef_region_ok(lo, hi, blob_bytes, g) || fb < 0 || fb > block_cap - g.nblocks) return;
+    const unsigned char* base = ws + reinterpret_cast<const long long*>(ws)[i];
+    RegionDst dst{blob + lo};
+    for (long long b = (long long)blockIdx.y * kBlock + threadIdx.x; b < g.nblocks; b += (long long)kBlock * gridDim.y) {
+        alignas(16) short coef[64];
+        load_block(base, b, coef);
+        const unsigned long long header = rkjpeg::coef_header_of(coef);
+        const long long at = block_off[fb + b];
+        if (at < rkjpeg::coef_table_bytes(g) || (at & 1) || at > hi - lo - rkjpeg::coef_record_bytes(header)) continue;
+        dst.put16(4 * b, (unsigned)at & 0xFFFFu);
+        dst.put16(4 * b + 2, (unsigned)(at >> 16) & 0xFFFFu);
+        rkjpeg::coef_pack_block(coef, header, dst, at);
+    }
+}
+
+// k_jpeg_plan for a batch of packed frames: the planes' regions of the workspace behind the offset table, every record
+// and its region of the blob checked from their own fields, flag[j] cleared.  offsets[j] is the planes' place MINUS
+// the frame's coefficient bytes, so that the plane offsets of rkjpeg::Geometry (which count from a region that starts
+// with the coefficients) land in the planes: k_jpeg_colour runs on this workspace as it is.
+__global__ __launch_bounds__(kBlock) void k_coef_plan(const rk_jpeg_frame* __restrict__ gathered, int m, long long rgb_bytes,
+                                                      int nq, const int* __restrict__ pick, const int* __restrict__ build_status,
+                                                      const long long* __restrict__ region_off, long long blob_bytes,
+                                                      long long* __restrict__ offsets, long long workspace_bytes,
+                                                      int* __restrict__ flag, int* __restrict__ status) {
+    __shared__ long long part[kBlock];
+    const int t = threadIdx.x, per = (m + kBlock - 1) / kBlock;
+    const int lo = min(m, t * per), hi = min(m, lo + per);
+    long long sum = 0;
+    for (int j = lo; j < hi; ++j) sum += rkjpeg::frame_plane_bytes(gathered[j]);
+    part[t] = sum;
+    __syncthreads();
+    long long at = rkjpeg::offset_table_bytes(m);
+    for (int k = 0; k < t; ++k) at += part[k];
+    for (int j = lo; j < hi; ++j) {
+        const rk_jpeg_frame f = gathered[j];
+        rkjpeg::Geometry g;
+        const bool sized = rkjpeg::geometry(f, g);
+        offsets[j] = at - (sized ? g.coef_bytes : 0);
+        at += sized ? rkjpeg::plane_bytes(g) : 0;
+        int rc = rkjpeg::check_coef_record(f, rgb_bytes, nq, at, workspace_bytes);
+        if (rc == RK_JPEG_OK) {                         // a pick outside the set is a zero record and was refused above
+            const int p = pick[j];
+            rc = build_status[p];
+            if (rc == RK_JPEG_OK && !rkjpeg::coef_region_ok(region_off[p], region_off[p + 1], blob_bytes, g)) rc = RK_JPEG_BAD_INDEX;
+        }
+        flag[j] = 0;
+        status[j] = rc;
+    }
+    if (t == kBlock - 1) offsets[m] = at;
+}
+
+__global__ __launch_bounds__(kBlock) void k_coef_idct(const rk_jpeg_frame* __restrict__ gathered,
+                                                      const unsigned short* __restrict__ qtabs,
+                                                      const unsigned char* __restrict__ blob, const long long* __restrict__ region_off,
+                                                      const int* __restrict__ pick, unsigned char* __restrict__ ws,
+                                                      const int* __restrict__ status, int* __restrict__ flag) {
+    const int j = blockIdx.x;
+    if (status[j] != RK_JPEG_OK) return;
+    const rk_jpeg_frame f = gathered[j];
+    rkjpeg::Geometry g;
+    rkjpeg::geometry(f, g);
+    const int p = pick[j];
+    const long long lo = region_off[p], len = region_off[p + 1] - lo;       // k_coef_plan has checked them
+    RegionSrc src{blob + lo};
+    unsigned char* base = ws + reinterpret_cast<const long long*>(ws)[j];
+    for (long long b = (long long)blockIdx.y * kBlock + threadIdx.x; b < g.nblocks; b += (long long)kBlock * gridDim.y) {
+        long long at;
+        unsigned long long header;
+        if (!rkjpeg::coef_block_ok(src, len, g, b, &at, &header)) {
+            flag[j] = 1;                                // the same word from every lane that refuses; k_coef_status reads it
+            continue;
+        }
+        int comp, stride;
+        long long off;
+        rkjpeg::block_place(g, b, &comp, &off, &stride);
+        alignas(16) short coef[64];
+        rkjpeg::coef_expand_block(src, at, header, coef);
+        const int qi = comp == 0 ? f.quant[0] : (comp == 1 ? f.quant[1] : f.quant[2]);
+        const long long plane = comp == 0 ? g.plane_off[0] : (comp == 1 ? g.plane_off[1] : g.plane_off[2]);
+        rkjpeg::idct_islow(coef, qtabs + (long long)qi * 64, base + plane + off, stride);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_coef_status(const int* __restrict__ flag, int m, int* __restrict__ status) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j < m && status[j] == RK_JPEG_OK && flag[j]) status[j] = RK_JPEG_BAD_INDEX;
+}
+
+// pick[j] = j: the slab's records are the entropy stage's "picked" frames, each once, in order.
+__global__ __launch_bounds__(kBlock) void k_coef_iota(int* __restrict__ pick, int n) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j < n) pick[j] = j;
+}
+
 // What the entry points ask of their arguments, in their order: pointers, then counts, sizes and alignment, then the workspace.
 bool any_null(std::initializer_list<const void*> ptrs) {
     for (const void* p : ptrs)
@@ -599,6 +834,98 @@ int rk_jpeg_decode_indexed_u8(const unsigned char* streams, long long stream_byt
     hipLaunchKernelGGL(k_jpeg_seg_status, dim3(groups), dim3(kBlock), 0, s, gathered, n_entries, entry_off, seg_mcus, build_status,
                        pick, segs, m, max_segments, status);
     hipLaunchKernelGGL(k_jpeg_idct, dim3(m, kIdctSlices), dim3(kBlock), 0, s, gathered, qtabs, ws, status);
+    hipLaunchKernelGGL(k_jpeg_colour, dim3(m, kColourSlices), dim3(kBlock), 0, s, gathered, ws, status, rgb, rgb_bytes);
+    hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, m);
+    return launch_status();
+}
+
+int rk_jpeg_coef_sizes(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                       const rk_jpeg_huff* htabs, int nq, int nh, int n, const rk_jpeg_entry* entries, long long n_entries,
+                       const long long* entry_off, const int* seg_mcus, const int* build_status, int max_segments,
+                       void* workspace, size_t workspace_bytes, int* status, unsigned* block_off, long long block_cap,
+                       long long* first_block, long long* region_off, rk_stream_t stream) {
+    using namespace rk;
+    if (any_null({streams, frames, htabs, status, block_off, first_block, region_off})) return RK_ERR_NULL_POINTER;
+    if (entries && any_null({entry_off, seg_mcus, build_status})) return RK_ERR_NULL_POINTER;
+    if (!counts_ok({n, nq, nh, max_segments}) || !sizes_ok({stream_bytes, n_entries, block_cap}) ||
+        !aligned(8, {frames, entries, entry_off, first_block, region_off}) ||
+        !aligned(4, {htabs, status, seg_mcus, build_status, block_off}))
+        return RK_ERR_BAD_DIMS;
+    const long long head = rkjpeg::indexed_head_bytes(n, max_segments);
+    if (!workspace_ok(workspace, workspace_bytes, head + rkjpeg::offset_table_bytes(n))) return RK_ERR_WORKSPACE;
+    const hipStream_t s = (hipStream_t)stream;
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    int* pick = reinterpret_cast<int*>(base);           // in the place of the gathered records, which are `frames` themselves
+    int* segs = reinterpret_cast<int*>(base + rkjpeg::gathered_bytes(n));
+    unsigned char* ws = base + head;
+    const long long ws_bytes = (long long)workspace_bytes - head;
+    const int groups = (n + kBlock - 1) / kBlock;
+    // a resident record has no place in an RGB arena and needs none here: any range is inside this one
+    hipLaunchKernelGGL(k_jpeg_plan, dim3(1), dim3(kBlock), 0, s, frames, n, stream_bytes, 1LL << 62, nq, nh,
+                       reinterpret_cast<long long*>(ws), ws_bytes, status);
+    if (entries) {
+        hipLaunchKernelGGL(k_coef_iota, dim3(groups), dim3(kBlock), 0, s, pick, n);
+        hipLaunchKernelGGL(k_jpeg_entropy_seg, dim3(n, max_segments), dim3(kWave), 0, s, streams, frames, htabs, entries, n_entries,
+                           entry_off, seg_mcus, build_status, pick, ws, status, segs);
+        hipLaunchKernelGGL(k_jpeg_seg_status, dim3(groups), dim3(kBlock), 0, s, frames, n_entries, entry_off, seg_mcus,
+                           build_status, pick, segs, n, max_segments, status);
+    } else {
+        hipLaunchKernelGGL(k_jpeg_entropy, dim3(n), dim3(kWave), 0, s, streams, frames, htabs, ws, status);
+    }
+    hipLaunchKernelGGL(k_coef_blocks, dim3(1), dim3(kBlock), 0, s, frames, n, block_cap, first_block, status);
+    hipLaunchKernelGGL(k_coef_block_sizes, dim3(n, kIdctSlices), dim3(kBlock), 0, s, frames, ws, status, first_block, block_off);
+    hipLaunchKernelGGL(k_coef_frame_scan, dim3(n), dim3(kBlock), 0, s, frames, status, first_block, block_off, region_off);
+    hipLaunchKernelGGL(k_coef_region_scan, dim3(1), dim3(kBlock), 0, s, region_off, n);
+    hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, n);
+    return launch_status();
+}
+
+int rk_jpeg_coef_pack(const rk_jpeg_frame* frames, int n, int max_segments, const void* workspace, size_t workspace_bytes,
+                      const int* status, const unsigned* block_off, long long block_cap, const long long* first_block,
+                      const long long* region_off, unsigned char* blob, long long blob_bytes, rk_stream_t stream) {
+    using namespace rk;
+    if (any_null({frames, status, block_off, first_block, region_off, blob})) return RK_ERR_NULL_POINTER;
+    if (!counts_ok({n, max_segments}) || !sizes_ok({block_cap, blob_bytes}) || !aligned(8, {frames, first_block, region_off}) ||
+        !aligned(4, {status, block_off}) || !aligned(2, {blob}))
+        return RK_ERR_BAD_DIMS;
+    const long long head = rkjpeg::indexed_head_bytes(n, max_segments);
+    if (!workspace_ok(workspace, workspace_bytes, head + rkjpeg::offset_table_bytes(n))) return RK_ERR_WORKSPACE;
+    const unsigned char* ws = static_cast<const unsigned char*>(workspace) + head;
+    hipLaunchKernelGGL(k_coef_pack, dim3(n, kIdctSlices), dim3(kBlock), 0, (hipStream_t)stream, frames, ws, status, block_off,
+                       block_cap, first_block, region_off, blob, blob_bytes);
+    return launch_status();
+}
+
+size_t rk_jpeg_coef_workspace_bytes(const rk_jpeg_frame* frames_host, int n, const int* pick_host, int m) {
+    if (!frames_host || !pick_host || n < 1 || m < 1) return 0;
+    long long total = rkjpeg::coef_head_bytes(m) + rkjpeg::offset_table_bytes(m);
+    for (int j = 0; j < m; ++j)
+        if (pick_host[j] >= 0 && pick_host[j] < n) total += rkjpeg::frame_plane_bytes(frames_host[pick_host[j]]);
+    return (size_t)total;
+}
+
+int rk_jpeg_decode_coef_u8(const unsigned char* blob, long long blob_bytes, const rk_jpeg_frame* frames,
+                           const unsigned short* qtabs, int nq, int n, const long long* region_off, const int* build_status,
+                           const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
+                           void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream) {
+    using namespace rk;
+    if (any_null({blob, frames, qtabs, region_off, build_status, pick, rgb_off, rgb, status})) return RK_ERR_NULL_POINTER;
+    if (n < 1 || !counts_ok({nq, m}) || !sizes_ok({blob_bytes, rgb_bytes}) || !aligned(8, {frames, region_off, rgb_off}) ||
+        !aligned(4, {status, build_status, pick}) || !aligned(2, {qtabs, blob}))
+        return RK_ERR_BAD_DIMS;
+    const long long head = rkjpeg::coef_head_bytes(m);
+    if (!workspace_ok(workspace, workspace_bytes, head + rkjpeg::offset_table_bytes(m))) return RK_ERR_WORKSPACE;
+    const hipStream_t s = (hipStream_t)stream;
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    rk_jpeg_frame* gathered = reinterpret_cast<rk_jpeg_frame*>(base);
+    int* flag = reinterpret_cast<int*>(base + rkjpeg::gathered_bytes(m));
+    unsigned char* ws = base + head;                    // an offset table, then planes only
+    const int groups = (m + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_jpeg_gather, dim3(groups), dim3(kBlock), 0, s, frames, n, pick, rgb_off, m, gathered);
+    hipLaunchKernelGGL(k_coef_plan, dim3(1), dim3(kBlock), 0, s, gathered, m, rgb_bytes, nq, pick, build_status, region_off,
+                       blob_bytes, reinterpret_cast<long long*>(ws), (long long)workspace_bytes - head, flag, status);
+    hipLaunchKernelGGL(k_coef_idct, dim3(m, kIdctSlices), dim3(kBlock), 0, s, gathered, qtabs, blob, region_off, pick, ws, status, flag);
+    hipLaunchKernelGGL(k_coef_status, dim3(groups), dim3(kBlock), 0, s, flag, m, status);
     hipLaunchKernelGGL(k_jpeg_colour, dim3(m, kColourSlices), dim3(kBlock), 0, s, gathered, ws, status, rgb, rgb_bytes);
     hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, m);
     return launch_status();

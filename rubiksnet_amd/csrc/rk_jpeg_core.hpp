@@ -1,8 +1,9 @@
 // rk_jpeg_core.hpp -- the baseline JPEG decode core of rk_jpeg.hip as plain host/device C++: record check and
 // geometry, bit reader, Huffman step, one scan's entropy decode -- whole, or a span of MCUs resumed at a recorded entry,
 // the walk that records those entries, and the same entries from many short walks in lock-step rounds -- jidctint's ISLOW
-// IDCT, fancy upsampling and YCbCr -> RGB.  The kernels only distribute this code over lanes; tests/jpeg_core_main.cpp,
-// tests/jpeg_index_main.cpp and tests/jpeg_chunked_main.cpp compile the same text for the CPU under AddressSanitizer /
+// IDCT, the packed form of a frame's coefficients with its checks, fancy upsampling and YCbCr -> RGB.  The kernels only
+// distribute this code over lanes; tests/jpeg_core_main.cpp, tests/jpeg_index_main.cpp, tests/jpeg_chunked_main.cpp and
+// tests/jpeg_coef_main.cpp compile the same text for the CPU under AddressSanitizer /
 // UBSan, which is the bounds proof for the kernels' logic.  That holds for everything in this file, the chunked build's
 // per-frame driver included: its phases are here, and what rk_jpeg.hip adds to them is barriers.  It does not hold for
 // what only rk_jpeg.hip has: the stream sources, the lane sink, the plan kernels' sums and the launch geometry.
@@ -775,6 +776,155 @@ RKJ_HD void block_place(const Geometry& g, long long b, int* comp, long long* of
         *offset = (long long)my * 8 * g.pcw + mx * 8;
     }
 }
+
+// ------------------------------------------------------------------------------------------------ packed coefficients
+// What the entropy stage leaves -- short[64] per block, natural order, not dequantised -- kept without its zeros
+// (rk_jpeg_coef_sizes / rk_jpeg_coef_pack / rk_jpeg_decode_coef_u8).  One frame's REGION, every part on a 2-byte boundary:
+//
+//   uint32 off[nblocks]    byte offset of block b's record from the region's start (blocks in block_place's order, MCU
+//                          padding blocks included); read and written as two 16-bit halves, low half first
+//   records, back to back, in block order: off[0] = 4 * nblocks, off[b + 1] = off[b] + bytes(b), the last one ends the region
+//
+//   record   uint64 header (four 16-bit words, lowest first): bit 0 = the AC values are 16-bit, bit k (1..63) = the AC
+//                   coefficient at zigzag position k is not zero
+//            int16  DC
+//            the non-zero AC values in zigzag order, int8 each where all of them fit, else int16 each (little endian),
+//            then one zero byte where that leaves an odd count:  10 + n * w rounded up to even, 10 .. 136 bytes
+//
+// The offsets make any block addressable on its own; the records still tile the region, which is what a reader checks:
+// every access is bounded from the frame's geometry (the table), the region's length (the 10 bytes of header and DC) and
+// the header (the values), and a block whose record does not end where the next one starts -- or the region, for the
+// last -- is refused, so no changed offset, header or length decodes as something else.  Geometry allows an 8x8 block
+// every one of the 63 AC positions, so the only header refused on its own is the one no packer writes: 16-bit values
+// with no value.
+// Src: `unsigned u16(long long at)` (at even) and `int s8(long long at)`, positions in bytes from the region's start.
+// Dst: `void put16(long long at, unsigned v)` (at even) and `void put8(long long at, int v)`.
+constexpr int kCoefRecordMin = 10, kCoefRecordMax = 136;
+
+RKJ_HD long long coef_table_bytes(const Geometry& g) { return g.nblocks * 4; }
+// The planes alone of a frame's workspace region (Geometry::bytes without the 128 bytes per block), a multiple of 16.
+RKJ_HD long long plane_bytes(const Geometry& g) { return g.bytes - g.coef_bytes; }
+RKJ_HD long long frame_plane_bytes(const rk_jpeg_frame& f) {
+    Geometry g;
+    return geometry(f, g) ? plane_bytes(g) : 0;
+}
+
+RKJ_HD int coef_ac_count(unsigned long long header) { return __builtin_popcountll(header >> 1); }
+RKJ_HD int coef_record_bytes(unsigned long long header) {
+    const int n = coef_ac_count(header), w = (header & 1) ? 2 : 1;
+    return kCoefRecordMin + ((n * w + 1) & ~1);
+}
+RKJ_HD bool coef_header_ok(unsigned long long header) { return (header & 1) == 0 || (header >> 1) != 0; }
+
+// The header of a block's 64 coefficients (natural order).
+RKJ_HD unsigned long long coef_header_of(const short* coef) {
+    unsigned long long mask = 0;
+    bool wide = false;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        const int v = coef[natural_of(k)];
+        if (v != 0) mask |= 1ull << k;
+        wide = wide || v < -128 || v > 127;
+    }
+    return mask | (wide ? 1ull : 0ull);
+}
+
+// Writes the block's record at `at`; coef_record_bytes(header) bytes, every one of them.
+template <class Dst>
+RKJ_HD void coef_pack_block(const short* coef, unsigned long long header, Dst& dst, long long at) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) dst.put16(at + 2 * h, (unsigned)(header >> (16 * h)) & 0xFFFFu);
+    dst.put16(at + 8, (unsigned)coef[0] & 0xFFFFu);
+    const bool wide = (header & 1) != 0;
+    long long p = at + kCoefRecordMin;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        if (!((header >> k) & 1)) continue;
+        const int v = coef[natural_of(k)];
+        if (wide) {
+            dst.put16(p, (unsigned)v & 0xFFFFu);
+            p += 2;
+        } else {
+            dst.put8(p, v);
+            p += 1;
+        }
+    }
+    if ((p - at) & 1) dst.put8(p, 0);
+}
+
+template <class Src>
+RKJ_HD unsigned long long coef_read_header(Src& src, long long at) {
+    unsigned long long header = 0;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) header |= (unsigned long long)(src.u16(at + 2 * h) & 0xFFFFu) << (16 * h);
+    return header;
+}
+
+// The record at `at` back into 64 coefficients (natural order); reads coef_record_bytes(header) bytes at most.  The
+// loop is unrolled with every index a constant, so that on the device coef[] stays in registers.
+template <class Src>
+RKJ_HD void coef_expand_block(Src& src, long long at, unsigned long long header, short* coef) {
+    coef[0] = (short)src.u16(at + 8);
+    const bool wide = (header & 1) != 0;
+    long long p = at + kCoefRecordMin;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        short v = 0;
+        if ((header >> k) & 1) {
+            if (wide) {
+                v = (short)src.u16(p);
+                p += 2;
+            } else {
+                v = (short)src.s8(p);
+                p += 1;
+            }
+        }
+        coef[natural_of(k)] = v;
+    }
+}
+
+// May bytes [lo, hi) of a blob of blob_bytes be frame g's region?  Inside the blob, on a 2-byte boundary, and long enough
+// for the table and the smallest record of every block (so the table can be read); at most what the blocks can take.
+RKJ_HD bool coef_region_ok(long long lo, long long hi, long long blob_bytes, const Geometry& g) {
+    if (lo < 0 || hi < lo || hi > blob_bytes || (lo & 1)) return false;
+    const long long len = hi - lo;
+    return len >= g.nblocks * (4 + kCoefRecordMin) && len <= g.nblocks * (4 + kCoefRecordMax);
+}
+
+RKJ_HD long long coef_offset_of(unsigned lo16, unsigned hi16) { return (long long)((lo16 & 0xFFFFu) | ((hi16 & 0xFFFFu) << 16)); }
+
+// Block b of a region that passed coef_region_ok: its offset from the table, inside the region with room for header and
+// DC before the header is read; then the header, and the record must end exactly where block b + 1 starts (the region,
+// for the last block).  true: *at and *header are the block's, and every byte of the record lies inside the region.
+template <class Src>
+RKJ_HD bool coef_block_ok(Src& src, long long region_len, const Geometry& g, long long b, long long* at,
+                          unsigned long long* header) {
+    const long long off = coef_offset_of(src.u16(4 * b), src.u16(4 * b + 2));
+    const long long end = b + 1 < g.nblocks ? coef_offset_of(src.u16(4 * b + 4), src.u16(4 * b + 6)) : region_len;
+    if ((off & 1) || off < coef_table_bytes(g) || off > region_len - kCoefRecordMin) return false;
+    if (b == 0 && off != coef_table_bytes(g)) return false;
+    const unsigned long long h = coef_read_header(src, off);
+    if (!coef_header_ok(h) || off + coef_record_bytes(h) != end || end > region_len) return false;
+    *at = off;
+    *header = h;
+    return true;
+}
+
+// A record that is decoded from a packed region: its sizes, its output range, its quantisation tables and ws_end, the
+// end of its planes in the workspace.  RK_JPEG_OK or RK_JPEG_BAD_RECORD.
+RKJ_HD int check_coef_record(const rk_jpeg_frame& f, long long rgb_bytes, int nq, long long ws_end, long long workspace_bytes) {
+    Geometry g;
+    if (!geometry(f, g)) return RK_JPEG_BAD_RECORD;
+    if (!rgb_range_ok(f, rgb_bytes)) return RK_JPEG_BAD_RECORD;
+    for (int c = 0; c < g.ncomp; ++c)
+        if (f.quant[c] >= nq) return RK_JPEG_BAD_RECORD;
+    if (ws_end > workspace_bytes) return RK_JPEG_BAD_RECORD;
+    return RK_JPEG_OK;
+}
+
+// Bytes in front of the planes in rk_jpeg_decode_coef_u8's workspace: the m gathered records, a flag per picked frame,
+// then the offset table.
+RKJ_HD long long coef_head_bytes(int m) { return gathered_bytes(m) + (((long long)m * 4 + 15) & ~15LL); }
 
 // ------------------------------------------------------------------------------------------------ upsampling and colour
 // One chroma sample at output pixel (x, y) as libjpeg's jdsample.c gives it.  plane: the component's plane, pitch pcw;

@@ -651,22 +651,34 @@ class DeviceFrameCache(_Feeder):
     counts them); frames the index build refused come out as zero frames, `decode_errors()` reads how many such frames
     went out so far.  index_build="chunked" (with resident="jpeg") builds the same index with
     rk_jpeg_build_index_chunked instead of one frame-long walk per frame (jpeg.build_index(method="chunked")); `index.route`
-    says which frames took which way.  A batch stays valid until the next one is asked for."""
+    says which frames took which way.
+
+    resident="coef" (the same sources) keeps what the Huffman stage leaves instead of the files: at construction
+    jpeg.build_coef transcodes the set once on the device, slab_frames frames at a time, into packed DCT coefficients (per
+    block an offset, a 64-bit mask, the DC and the non-zero AC values; index_build chooses the slabs' entropy stage), and
+    per batch one rk_jpeg_decode_coef_u8 launch -- no Huffman stage, the same IDCT on the same coefficients -- fills the
+    RGB arena: the same sampling, boxes, fallback frames and bit-identical clips, a batch launch some tens of times
+    shorter than "jpeg"'s, a footprint between the two others' (content decides: noisy frames pack poorly), and a
+    construction that takes the transcode's time.  budget_bytes counts the packed blob, its tables, the records, the
+    host-decoded frames, the batch buffers and, while the build runs, a slab's buffers; it is asked before every
+    allocation of the build.  A batch stays valid until the next one is asked for."""
 
     def __init__(self, source, batch, split, device="cuda:0", dtype=torch.float32, size=224, views=1, box_fn=None, seed=0,
                  temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5, budget_bytes=4 << 30, resident="rgb",
-                 index_build="chain", **sampling):
-        if resident not in ("rgb", "jpeg"):
-            raise ValueError("resident must be 'rgb' or 'jpeg', got %r" % (resident,))
+                 index_build="chain", slab_frames=256, **sampling):
+        self.slab_frames = int(slab_frames)
+        if resident not in ("rgb", "jpeg", "coef"):
+            raise ValueError("resident must be 'rgb' or 'jpeg' or 'coef', got %r" % (resident,))
         if index_build not in ("chain", "chunked"):
             raise ValueError("index_build must be 'chain' or 'chunked', got %r" % (index_build,))
-        if index_build == "chunked" and resident != "jpeg":
-            raise ValueError("index_build='chunked' builds the scan index of resident files: it goes with resident='jpeg', not "
-                             "%r" % (resident,))
+        if index_build == "chunked" and resident not in ("jpeg", "coef"):
+            raise ValueError("index_build='chunked' builds the scan index of resident files: it goes with resident='jpeg' or "
+                             "'coef', not %r" % (resident,))
         self.index_build = index_build
-        if resident == "jpeg" and not (isinstance(source, RubiksDataset) and source.decode == "device"):
-            raise ValueError("resident='jpeg' keeps the files' bytes: it needs a RubiksDataset(..., decode='device'), not "
-                             "%s" % ("in-memory videos, which are decoded already" if not isinstance(source, RubiksDataset)
+        if resident in ("jpeg", "coef") and not (isinstance(source, RubiksDataset) and source.decode == "device"):
+            raise ValueError("resident=%r %s: it needs a RubiksDataset(..., decode='device'), not "
+                             "%s" % (resident, "keeps the files' bytes" if resident == "jpeg" else "transcodes the files",
+                                     "in-memory videos, which are decoded already" if not isinstance(source, RubiksDataset)
                                      else "a decode='host' dataset"))
         if not isinstance(source, _Sampled):
             videos, labels = zip(*source) if len(source) else ((), ())
@@ -681,7 +693,7 @@ class DeviceFrameCache(_Feeder):
         self.source, self.drop_last = source, drop_last
         self.shuffle = (split == "train") if shuffle is None else shuffle
         self.resident, self.budget_bytes, self.fallback_frames = resident, int(budget_bytes), 0
-        if resident == "jpeg":
+        if resident in ("jpeg", "coef"):
             self._init_jpeg()
             return
         need, whole = 0, []
@@ -705,6 +717,9 @@ class DeviceFrameCache(_Feeder):
         self.records = torch.cat([torch.zeros(len(res.videos), 1, dtype=torch.int64), res.videos[:, [2, 3, 1]]], dim=1)
         sizes = [f.numel() for f in res.fallback]
         self._fallback_off = [0] + np.cumsum(sizes).tolist()
+        if self.resident == "coef":
+            self._init_coef(sizes)
+            return
         n_entries = int(res.entry_off[-1])
         tables = res.seg_mcus.numel() * 4 + res.entry_off.numel() * 8 + (int(res.layout[0]) + 1) * 4
         if self.index_build == "chunked":
@@ -724,18 +739,47 @@ class DeviceFrameCache(_Feeder):
         self._dev_labels = self.labels.to(self.device)
         _mean_std_on(self.device, IMAGENET_MEAN, IMAGENET_STD)
 
+    def _init_coef(self, sizes):
+        """resident="coef": the files transcoded once, slab by slab, into packed coefficients (jpeg.build_coef).  The budget
+        is asked before every allocation of the build -- the finished parts of the blob, the slab's buffers, the
+        host-decoded frames -- so a set that does not fit raises before the device holds it."""
+        res, fallback = self.packed, sum(sizes)
+
+        self.build_peak_bytes = 0
+
+        def admit(held):
+            self.build_peak_bytes = max(self.build_peak_bytes, held + fallback)
+            if held + fallback > self.budget_bytes:
+                raise RuntimeError("DeviceFrameCache: transcoding the %d videos takes %d bytes on the device, over the budget "
+                                   "of %d bytes; raise budget_bytes or stream with FrameLoader"
+                                   % (len(self.source), held + fallback, self.budget_bytes))
+
+        self.coef = jpeg.build_coef(res, self.device, method=self.index_build, slab_frames=self.slab_frames, admit=admit)
+        n = self.coef.n
+        self._fixed_bytes = self.coef.blob.numel() + n * 64 + self.coef.qtabs.numel() + (n + 1) * 12 + fallback
+        self._fallback = torch.empty(fallback, dtype=torch.uint8, device=self.device)
+        for frame, at in zip(res.fallback, self._fallback_off):
+            self._fallback[at:at + frame.numel()].copy_(frame.reshape(-1))
+        self._host_frames = jpeg.records(res.blob, res.layout).copy()
+        self._frame_ws = jpeg.frame_plane_bytes(self._host_frames)
+        self._rgb = self._ws = self._status = None
+        self._errors = torch.zeros((), dtype=torch.int64, device=self.device)
+        self._dev_labels = self.labels.to(self.device)
+        _mean_std_on(self.device, IMAGENET_MEAN, IMAGENET_STD)
+
     @property
     def resident_bytes(self):
-        """Bytes of HBM the cache holds now: the arena ("rgb"), or the blob, the index, the host-decoded frames and the
-        batch buffers as far as they have grown ("jpeg")."""
+        """Bytes of HBM the cache holds now: the arena ("rgb"); the blob, the index, the host-decoded frames and the
+        batch buffers as far as they have grown ("jpeg"); the packed blob, its tables, the records, the host-decoded frames
+        and the batch buffers ("coef"; the build's slab buffers are gone by the time anyone can ask)."""
         if self.resident == "rgb":
             return self.arena.numel()
         return self._fixed_bytes + sum(t.numel() * t.element_size() for t in (self._rgb, self._ws, self._status) if t is not None)
 
     def decode_errors(self):
-        """Frames that went out as zero frames so far because the device refused them (resident="jpeg"; 0 otherwise).
-        Waits for the device: ask once, at the end of an epoch."""
-        return int(self._errors.item()) if self.resident == "jpeg" else 0
+        """Frames that went out as zero frames so far because the device refused them (resident="jpeg" or "coef"; 0
+        otherwise).  Waits for the device: ask once, at the end of an epoch."""
+        return int(self._errors.item()) if self.resident != "rgb" else 0
 
     def _grown(self, t, need, make):
         """FrameLoader._grown under the budget: the batch buffers grow on demand, and count."""
@@ -756,14 +800,20 @@ class DeviceFrameCache(_Feeder):
         self._rgb = self._grown(self._rgb, t.rgb_bytes, lambda k: torch.empty(k, dtype=torch.uint8, device=self.device))
         rgb = self._rgb[:t.rgb_bytes]
         if m:
-            need = jpeg.indexed_workspace_bytes_for(self._host_frames, t.pick.numpy(), t.max_segments, self._frame_ws)
+            if self.resident == "coef":
+                need = jpeg.coef_workspace_bytes_for(self._host_frames, t.pick.numpy(), self._frame_ws)
+            else:
+                need = jpeg.indexed_workspace_bytes_for(self._host_frames, t.pick.numpy(), t.max_segments, self._frame_ws)
             self._ws = self._grown(self._ws, need, lambda k: torch.empty(k, dtype=torch.uint8, device=self.device))
             self._status = self._grown(self._status, m + 1, lambda k: torch.zeros(k, dtype=torch.int32, device=self.device))
             with _near_gpu(self.device):
                 pick, rgb_off = t.pick.pin_memory(), t.rgb_off.pin_memory()
             status = self._status[:m + 1]
-            jpeg.launch_decode_indexed(self.index, pick.to(self.device, non_blocking=True),
-                                       rgb_off.to(self.device, non_blocking=True), t.max_segments, rgb, self._ws, status)
+            pick, rgb_off = pick.to(self.device, non_blocking=True), rgb_off.to(self.device, non_blocking=True)
+            if self.resident == "coef":
+                jpeg.launch_decode_coef(self.coef, pick, rgb_off, rgb, self._ws, status)
+            else:
+                jpeg.launch_decode_indexed(self.index, pick, rgb_off, t.max_segments, rgb, self._ws, status)
             self._errors += status[m]
         for f, off in t.fallback:
             at, k = self._fallback_off[f], self._fallback_off[f + 1] - self._fallback_off[f]
@@ -780,8 +830,8 @@ class DeviceFrameCache(_Feeder):
         for b in range(len(self)):
             ids = order[b * self.batch:(b + 1) * self.batch]
             clips = self.records[ids]
-            if self.resident == "jpeg":
-                numbers = [(torch.tensor(self.source.frame_numbers(nf, self._gen), dtype=torch.int64).clamp_(1, nf) - 1).tolist()
+            if self.resident != "rgb":
+                numbers =[(torch.tensor(self.source.frame_numbers(nf, self._gen), dtype=torch.int64).clamp_(1, nf) - 1).tolist()
                            for nf in clips[:, 3].tolist()]
                 boxes = self._boxes([(int(h), int(w)) for h, w in clips[:, 1:3].tolist()])
                 arena, clips, local = self._decode_batch(ids, numbers)

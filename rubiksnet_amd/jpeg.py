@@ -25,6 +25,13 @@ A streamed batch can take the row-parallel decoder too (decode_jpeg_frames(entro
 row_tables makes the index tables of the batch's own records on the host, one segment per MCU row, the chunked build
 finds the entries on the device and rk_jpeg_decode_indexed_u8 decodes every record to its own place.
 
+A resident set can also be kept as what the Huffman stage leaves (dataset.DeviceFrameCache(resident="coef")):
+
+  build_coef             the set transcoded once, slab by slab, into packed DCT coefficients (rk_jpeg_coef_sizes,
+                         rk_jpeg_coef_pack): per block an offset, a 64-bit mask, the DC and the non-zero AC values
+  launch_decode_coef     the per-batch launch (rk_jpeg_decode_coef_u8): no Huffman stage, the same IDCT on the same
+                         coefficients; pick_tables as above
+
 There is no CPU path: a missing library is an error (tests compare with Pillow).
 """
 import collections
@@ -38,7 +45,7 @@ __all__ = ["JpegHeader", "parse_jpeg", "pack_jpeg_clips", "PackedJpeg", "decode_
            "ResidentJpeg", "pack_resident", "DeviceIndex", "build_index", "PickTables", "pick_tables",
            "frame_workspace_bytes", "indexed_workspace_bytes_for", "launch_decode_indexed", "chunked_workspace_bytes_for",
            "launch_build_index_chunked", "RowTables", "row_tables", "launch_decode_rows", "CHUNK_BYTES", "MAX_ROUNDS",
-           "MAX_CHUNKS"]
+           "MAX_CHUNKS", "DeviceCoef", "build_coef", "frame_plane_bytes", "coef_workspace_bytes_for", "launch_decode_coef"]
 
 MAX_SIDE = 16384
 STATUS_NAMES = ("ok", "bad record", "bad code", "run past 63", "truncated", "bad restart", "trailing data", "bad value",
@@ -233,18 +240,23 @@ def _align16(v):
     return (v + 15) & ~15
 
 
-def _geometry(frames):
-    """rkjpeg::geometry of a FRAME_DTYPE array, in numpy -> (ok, mcux, mcuy, bytes), each per record: are its sizes
-    valid, its MCUs per row and per column (1 where they are not), the bytes of its region of the workspace (0 where
-    they are not: 128 of coefficients and 64 of samples per block, rounded up to 16)."""
+def _geometry_blocks(frames):
+    """rkjpeg::geometry of a FRAME_DTYPE array, in numpy -> (ok, mcux, mcuy, blocks), each per record: are its sizes
+    valid, its MCUs per row and per column (1 where they are not), its 8x8 blocks (0 where they are not)."""
     f = np.asarray(frames).reshape(-1)
     w, h, nc, s = (f[k].astype(np.int64) for k in ("width", "height", "components", "sampling"))
     ok = (w >= 1) & (w <= MAX_SIDE) & (h >= 1) & (h <= MAX_SIDE) & ((nc == 1) | ((nc == 3) & (s >= 0) & (s <= 2)))
     hs, vs = np.where((nc == 3) & (s >= 1), 2, 1), np.where((nc == 3) & (s == 2), 2, 1)
     mcux = np.where(ok, (w + 8 * hs - 1) // (8 * hs), 1)
     mcuy = np.where(ok, (h + 8 * vs - 1) // (8 * vs), 1)
-    blocks = mcux * mcuy * np.where(nc == 1, 1, hs * vs + 2)
-    return ok, mcux, mcuy, np.where(ok, _align16(blocks * 192), 0)
+    return ok, mcux, mcuy, np.where(ok, mcux * mcuy * np.where(nc == 1, 1, hs * vs + 2), 0)
+
+
+def _geometry(frames):
+    """-> (ok, mcux, mcuy, bytes) per record: _geometry_blocks with, for the blocks, the bytes of the record's region of
+    the workspace (0 where its sizes are not valid: 128 of coefficients and 64 of samples per block, rounded up to 16)."""
+    ok, mcux, mcuy, blocks = _geometry_blocks(frames)
+    return ok, mcux, mcuy, _align16(blocks * 192)
 
 
 def _mcus(width, height, components, sampling):
@@ -611,6 +623,157 @@ def launch_decode_indexed(index, pick, rgb_off, max_segments, rgb, workspace, st
                    index.entries.data_ptr(), index.n_entries, index.entry_off.data_ptr(), index.seg_mcus.data_ptr(),
                    index.status.data_ptr(), pick.data_ptr(), rgb_off.data_ptr(), m, int(max_segments), rgb.data_ptr(),
                    rgb.numel(), workspace.data_ptr(), workspace.numel(), status.data_ptr())
+
+
+# ------------------------------------------------------------------------------------------------- packed coefficients
+DeviceCoef = collections.namedtuple("DeviceCoef", [
+    "blob",             # uint8 on the device: every frame's region (offset table, block records), back to back in its first
+                        # packed_bytes bytes; what the estimate left over follows
+    "region_off",       # int64 [n + 1] on the device: frame i's region is blob[region_off[i]:region_off[i + 1]]
+    "frames", "qtabs",  # uint8 on the device: the n records and the quantisation tables
+    "n", "nq",
+    "status",           # int32 [n + 1] on the device: the entropy stage's code per frame, [n] their count
+    "packed_bytes",     # bytes of all regions
+    "file_bytes",       # bytes of the same frames' entropy-coded segments, what resident="jpeg" would keep of them
+    "build_bytes",      # the most the build held on the device beside the blob and the tables (one slab's buffers)
+])
+
+COEF_RECORD_MIN, COEF_RECORD_MAX = 10, 136
+
+
+def frame_plane_bytes(frames):
+    """int64 per record of a FRAME_DTYPE array: the bytes of its component planes in rk_jpeg_decode_coef_u8's workspace
+    (64 per block, rounded up to 16; 0 for sizes that are not valid)."""
+    blocks = _geometry_blocks(frames)[3]
+    return _align16(blocks * 192) - blocks * 128
+
+
+def coef_workspace_bytes_for(frames, pick, per_frame=None):
+    """rk_jpeg_coef_workspace_bytes of a FRAME_DTYPE array and a pick list, in numpy: the gathered records, a flag per
+    picked frame, the offset table, the picked frames' planes.  per_frame: frame_plane_bytes of `frames`, where the
+    caller keeps it."""
+    frames, pick = np.asarray(frames).reshape(-1), np.asarray(pick, dtype=np.int64).reshape(-1)
+    if frames.size < 1 or pick.size < 1:
+        return 0
+    per_frame = frame_plane_bytes(frames) if per_frame is None else per_frame
+    inside = pick[(pick >= 0) & (pick < frames.size)]
+    return pick.size * 64 + _align16(pick.size * 4) + _align16((pick.size + 1) * 8) + int(per_frame[inside].sum())
+
+
+def _as_bytes(arr, device):
+    return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).reshape(-1).copy()).to(device)
+
+
+def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk_bytes=256, max_rounds=32, admit=None):
+    """A ResidentJpeg transcoded on the device into packed DCT coefficients (rk_jpeg_coef_sizes, rk_jpeg_coef_pack): every
+    frame's Huffman code is undone once, here.  The set goes through in slabs of slab_frames frames: a slab's file bytes
+    and records are uploaded, its entropy stage runs -- method="chain": one chain per frame; method="chunked": the scan
+    index of the slab from rk_jpeg_build_index_chunked (chunk_bytes, max_rounds), then one chain per segment -- its blocks
+    are measured, the host reads the slab's total, and the records are written behind those of the slabs before it;
+    then the slab's buffers are dropped, so the file bytes, the index entries and the 128-byte-per-block workspace never
+    exist for more than one slab.  The blob is allocated once the first slab is measured, at that slab's bytes per frame
+    for the whole set plus 3 % (and again, larger, should a later slab not fit).  admit(bytes): called before every
+    allocation with the bytes the build is about to hold on the device (the blob included); it may raise.  Returns a
+    DeviceCoef.  The host waits once per slab."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("build_coef runs on a GPU (no CPU path)")
+    if method not in ("chain", "chunked"):
+        raise ValueError("method must be 'chain' or 'chunked', got %r" % (method,))
+    if not 1 <= int(slab_frames) <= MAX_LAUNCH:
+        raise ValueError("slab_frames must be in [1, %d], got %r" % (MAX_LAUNCH, slab_frames))
+    if method == "chunked":
+        _check_chunking(chunk_bytes, max_rounds)
+    from . import _native
+    admit = admit or (lambda held: None)
+    (frames_h, htabs_h, qtabs_h, streams_h), (n, nh, nq) = sections(resident.blob, resident.layout)
+    rec = records(resident.blob, resident.layout).copy()
+    blocks = _geometry_blocks(rec)[3]
+    fixed = frames_h.numel() + qtabs_h.numel() + (n + 1) * 12
+    admit(fixed + htabs_h.numel())
+    frames, qtabs, htabs = frames_h.to(device), qtabs_h.to(device), htabs_h.to(device)
+    region_off = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    status = torch.zeros(n + 1, dtype=torch.int32, device=device)
+    blob, room, done, most_held = None, 0, 0, 0
+    for lo in range(0, n, int(slab_frames)):
+        hi = min(n, lo + int(slab_frames))
+        k = hi - lo
+        slab = rec[lo:hi].copy()
+        first = int(slab["stream_off"].min())
+        last = int((slab["stream_off"] + slab["stream_len"]).max())
+        slab["stream_off"] -= first
+        most = int(resident.segments[lo:hi].max()) if method == "chunked" else 1
+        ws_bytes = indexed_workspace_bytes_for(slab, np.arange(k), most)
+        cap = max(int(blocks[lo:hi].sum()), 1)
+        held = (last - first) + k * 64 + ws_bytes + cap * 4 + (k + 1) * 20
+        if method == "chunked":
+            eo = (resident.entry_off[lo:hi + 1] - resident.entry_off[lo]).contiguous()
+            n_entries = int(eo[-1])
+            build_ws_bytes = chunked_workspace_bytes_for(slab, chunk_bytes)
+            held += max(n_entries, 1) * 16 + build_ws_bytes + k * 16 + 12
+        admit(fixed + htabs_h.numel() + room + held)
+        most_held = max(most_held, held)
+        streams = streams_h[first:last].to(device) if last > first else torch.zeros(1, dtype=torch.uint8, device=device)
+        slab_d = _as_bytes(slab, device)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        block_off = torch.empty(cap, dtype=torch.int32, device=device)
+        first_block = torch.empty(k + 1, dtype=torch.int64, device=device)
+        rel = torch.empty(k + 1, dtype=torch.int64, device=device)
+        part_status = torch.zeros(k + 1, dtype=torch.int32, device=device)
+        index = (None, 0, None, None, None)
+        if method == "chunked":
+            seg_mcus, entry_off = resident.seg_mcus[lo:hi].contiguous().to(device), eo.to(device)
+            entries = torch.zeros(max(n_entries, 1) * 2, dtype=torch.int64, device=device).view(torch.uint8)
+            build_status = torch.zeros(k + 1, dtype=torch.int32, device=device)
+            route = torch.zeros(k, dtype=torch.int32, device=device)
+            launch_build_index_chunked(streams, slab_d, htabs, nq, nh, k, seg_mcus, entry_off, entries, n_entries, chunk_bytes,
+                                       max_rounds, torch.empty(build_ws_bytes, dtype=torch.uint8, device=device), build_status,
+                                       route)
+            index = (entries.data_ptr(), n_entries, entry_off.data_ptr(), seg_mcus.data_ptr(), build_status.data_ptr())
+        _native.launch("rk_jpeg_coef_sizes", device, streams.data_ptr(), streams.numel(), slab_d.data_ptr(), htabs.data_ptr(), nq,
+                       nh, k, *index, most, ws.data_ptr(), ws.numel(), part_status.data_ptr(), block_off.data_ptr(), cap,
+                       first_block.data_ptr(), rel.data_ptr())
+        total = int(rel[k].item())                      # the host waits here, once per slab
+        if blob is None or done + total > room:
+            # the blob is one allocation that the slabs fill in turn: its size is the first slab's bytes a frame carried over
+            # to the whole set, with 3 % to spare (the last slab knows the size); where a later slab still does not fit,
+            # a larger one takes over what is packed so far -- only then do two blobs exist at once
+            want = max(_align16(int((done + total) * (1.0 if hi == n else 1.03 * n / hi))), 16)
+            admit(fixed + htabs_h.numel() + room + held + want)
+            grown = torch.empty(want, dtype=torch.uint8, device=device)
+            if done:
+                grown[:done].copy_(blob[:done])
+            blob, room = grown, want
+            del grown
+        rel += done
+        _native.launch("rk_jpeg_coef_pack", device, slab_d.data_ptr(), k, most, ws.data_ptr(), ws.numel(), part_status.data_ptr(),
+                       block_off.data_ptr(), cap, first_block.data_ptr(), rel.data_ptr(), blob.data_ptr(), room)
+        region_off[lo:hi + 1].copy_(rel)
+        status[lo:hi].copy_(part_status[:k])
+        status[n] += part_status[k]
+        done += total
+        torch.cuda.current_stream(device).synchronize()   # the slab's buffers go back before the next slab asks for its own
+        del streams, slab_d, ws, block_off, first_block, rel, part_status, index
+    del htabs
+    if blob is None:                                    # no frame at all: sixteen bytes that no region lies in
+        blob = torch.zeros(16, dtype=torch.uint8, device=device)
+    return DeviceCoef(blob, region_off, frames, qtabs, n, nq, status, done, int(rec["stream_len"].sum()), most_held)
+
+
+def launch_decode_coef(coef, pick, rgb_off, rgb, workspace, status):
+    """rk_jpeg_decode_coef_u8 on the current stream.  coef: a DeviceCoef; pick int32 [m], rgb_off int64 [m], rgb uint8
+    [rgb_bytes], workspace uint8 (16-byte aligned, coef_workspace_bytes_for), status int32 [m + 1]: device tensors.  Nothing
+    is allocated and the host does not wait."""
+    from . import _native
+    m = pick.numel()
+    _check_tensors((("pick", pick, torch.int32), ("rgb_off", rgb_off, torch.int64), ("rgb", rgb, torch.uint8),
+                    ("workspace", workspace, torch.uint8), ("status", status, torch.int32)))
+    if rgb_off.numel() != m or status.numel() < m + 1:
+        raise ValueError("pick [%d], rgb_off [%d], status [%d]: want m, m, m + 1" % (m, rgb_off.numel(), status.numel()))
+    _native.launch("rk_jpeg_decode_coef_u8", rgb.device, coef.blob.data_ptr(), coef.packed_bytes, coef.frames.data_ptr(),
+                   coef.qtabs.data_ptr(), coef.nq, coef.n, coef.region_off.data_ptr(), coef.status.data_ptr(), pick.data_ptr(),
+                   rgb_off.data_ptr(), m, rgb.data_ptr(), rgb.numel(), workspace.data_ptr(), workspace.numel(),
+                   status.data_ptr())
 
 
 # ------------------------------------------------------------------------------------------------- a streamed batch by rows
