@@ -918,6 +918,50 @@ int rk_jpeg_decode_coef_u8(const unsigned char* blob, long long blob_bytes, cons
                            const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
                            void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream);
 
+/* ---- a second, denser record format for the same packed set (rk_jpeg.hip) ----
+ * The three entry points above with a trailing record_format: RK_JPEG_COEF_WIDE is the format above, and the functions
+ * above ARE these with it; RK_JPEG_COEF_DENSE chooses the value class per coefficient, not per block -- video frames
+ * have one to three large values a block and some 25 within +-7 -- and a table of half the size.  Every other argument,
+ * the workspace, block_off (the absolute offset of a block's record in its region), the launches and the return codes
+ * are as above; any other record_format returns RK_ERR_BAD_DIMS.  A blob is decoded with the format it was packed in.
+ * One frame's DENSE region (little endian, every record on a 2-byte boundary, no padding between regions):
+ *   uint32 base[G], G = ceil(nblocks / 64), then uint16 rel[nblocks]: block b's record starts base[b / 64] + rel[b]
+ *   bytes from the region's start (the packer writes base[g] = the start of record 64 g); the table is 4 G + 2 nblocks
+ *   bytes, the first record starts there, record b + 1 starts where record b ends, the last one ends the region
+ *   ordinary record: uint8 tag (bits 0-5 `last`, the zigzag position of the last non-zero AC, 0: none; bits 6-7 the
+ *           class), int16 DC, ceil(last / 8) mask bytes (bit j: the AC at zigzag position j + 1 is not zero), ceil(n / 2)
+ *           bytes of nibbles, one per non-zero AC in zigzag order, low nibble first (the value in 4-bit two's complement
+ *           where it lies in -7 .. 7, 0x8: escaped), the e escaped values in order (int8 each in class 0; int16 each in
+ *           class 1, used when one leaves int8), a zero byte to an even length:
+ *           roundup2(3 + ceil(last / 8) + ceil(n / 2) + e w), 4 .. 130 bytes
+ *   raw record (class 2), where the ordinary one would exceed 130 bytes: tag 0x80, a zero byte, int16[64] in natural order
+ * RK_JPEG_BAD_INDEX and a zero frame, before anything outside the frame's region is read: a region not inside the blob,
+ * odd at either end, or not between the table plus 4 and the table plus 130 bytes per block; a record start inside the
+ * table, odd or less than 4 bytes from the region's end; a first record not at the table's end; a span [start, next
+ * start) outside 4 .. 130 bytes; a record whose length, from its own tag, mask, nibbles and class, is not its span;
+ * class 3; raw with last != 0; a mask whose bit `last` is clear or that has a bit above it; a nibble of 0 for a
+ * coefficient the mask names.  The span comes from the table alone and every read of a record is checked against it
+ * first.  What the format cannot see: a change that keeps every one of these true, such as a class bit flipped on a
+ * record with a single escaped value whose padding absorbs the difference.
+ * rk_jpeg_coef_region_bounds: the least and the most bytes a frame of nblocks blocks takes in `format` (table
+ * included); host only; RK_ERR_BAD_DIMS for another format or nblocks < 1.                                             */
+#define RK_JPEG_COEF_WIDE 0
+#define RK_JPEG_COEF_DENSE 1
+int rk_jpeg_coef_sizes_as(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                          const rk_jpeg_huff* htabs, int nq, int nh, int n, const rk_jpeg_entry* entries, long long n_entries,
+                          const long long* entry_off, const int* seg_mcus, const int* build_status, int max_segments,
+                          void* workspace, size_t workspace_bytes, int* status, unsigned* block_off, long long block_cap,
+                          long long* first_block, long long* region_off, rk_stream_t stream, int record_format);
+int rk_jpeg_coef_pack_as(const rk_jpeg_frame* frames, int n, int max_segments, const void* workspace, size_t workspace_bytes,
+                         const int* status, const unsigned* block_off, long long block_cap, const long long* first_block,
+                         const long long* region_off, unsigned char* blob, long long blob_bytes, rk_stream_t stream,
+                         int record_format);
+int rk_jpeg_decode_coef_as_u8(const unsigned char* blob, long long blob_bytes, const rk_jpeg_frame* frames,
+                              const unsigned short* qtabs, int nq, int n, const long long* region_off, const int* build_status,
+                              const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
+                              void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream, int record_format);
+int rk_jpeg_coef_region_bounds(int record_format, long long nblocks, long long* min_bytes, long long* max_bytes);
+
 /* ---- squeeze-and-excitation gate of RubiksNet-Small -- widening row f3 of SURVEY 8(f) --------------
  * SELayer (rubiksnet/backbone.py:56-71): y = x * sigmoid(W2 relu(W1 mean_hw(x))).  x, y, dy, dx [F, C, P];
  * mean / gate / dgate [F, C] f32.  squeeze: mean over P; scale: y = x * gate; scale_backward: dx = dy * gate and

@@ -188,6 +188,11 @@ SIGNATURES["rk_jpeg_coef_pack"] = (_i, [_p, _i, _i, _p, _sz, _p, _p, ctypes.c_lo
 SIGNATURES["rk_jpeg_coef_workspace_bytes"] = (_sz, [_p, _i, _p, _i])
 SIGNATURES["rk_jpeg_decode_coef_u8"] = (_i, [_p, ctypes.c_longlong, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, ctypes.c_longlong, _p, _sz,
                                              _p, _p])
+# the same three with a trailing record_format (behind the stream); format, nblocks, &least, &most -> status
+for _name, _as in (("rk_jpeg_coef_sizes", "rk_jpeg_coef_sizes_as"), ("rk_jpeg_coef_pack", "rk_jpeg_coef_pack_as"),
+                   ("rk_jpeg_decode_coef_u8", "rk_jpeg_decode_coef_as_u8")):
+    SIGNATURES[_as] = (_i, SIGNATURES[_name][1] + [_i])
+SIGNATURES["rk_jpeg_coef_region_bounds"] = (_i, [_i, ctypes.c_longlong, _p, _p])
 for _sfx in ("f32", "bf16"):
     SIGNATURES["rk_clip_u8_to_chw_" + _sfx] = (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p])
     SIGNATURES["rk_clip_resample_u8_" + _sfx] = (_i, [_p] * 5 + [_i] * 7 + [_p])     # B,T,Hs,Ws,V,Sh,Sw
@@ -248,10 +253,11 @@ def call(name, *args):
         check(rc, name)
 
 
-def launch(name, dev, *args):
-    """`call` with device `dev` current and its current stream's handle as the last argument."""
+def launch(name, dev, *args, after=()):
+    """`call` with device `dev` current and its current stream's handle as the last argument (`after`: what the entry
+    point takes behind the stream)."""
     with torch.cuda.device(dev):
-        call(name, *args, torch.cuda.current_stream(dev).cuda_stream)
+        call(name, *args, torch.cuda.current_stream(dev).cuda_stream, *after)
 
 
 def ptr(t):

@@ -483,6 +483,16 @@ __global__ __launch_bounds__(kBlock) void k_jpeg_count(int* __restrict__ status,
 // small fraction of what HBM gives) and a lane's LDS reads would be as scattered as its global ones.  The expansion is
 // unrolled over the 63 positions with constant indices, so the block stays in registers and goes into idct_islow as
 // k_jpeg_idct's does.
+//
+// The entry points with a trailing record_format (rk_jpeg_coef_sizes_as, rk_jpeg_coef_pack_as, rk_jpeg_decode_coef_as_u8)
+// are the drivers; the ones without are calls of them with RK_JPEG_COEF_WIDE.  The format is a template policy of
+// k_coef_block_sizes, k_coef_pack and k_coef_idct (WideRecords, DenseRecords below) and a number to k_coef_frame_scan and
+// k_coef_plan, which need the table's size and the region's bounds; every other kernel does not know it.  With
+// DenseRecords the lane of k_coef_idct takes its record's span from the table (a base per 64 blocks and a 16-bit distance
+// per block), holds the mask in one 64-bit register and takes the nibbles from a 32-bit window that is refilled every
+// eighth nibble from an address that the count of nibbles taken gives -- the mask alone decides it -- so that only an
+// escaped value's load waits for loaded data; every read is checked against the span first and the record must fill
+// it exactly (rkjpeg::dense_expand_block).  The same unrolled loop, the same registers: 0 bytes of scratch.
 struct RegionSrc {          // a region of the blob, 2-byte aligned
     const unsigned char* p;
     __device__ __forceinline__ unsigned u16(long long at) const { return *reinterpret_cast<const unsigned short*>(p + at); }
@@ -492,6 +502,71 @@ struct RegionDst {
     unsigned char* p;
     __device__ __forceinline__ void put16(long long at, unsigned v) { *reinterpret_cast<unsigned short*>(p + at) = (unsigned short)v; }
     __device__ __forceinline__ void put8(long long at, int v) { p[at] = (unsigned char)v; }
+};
+
+// The record format as a policy of k_coef_block_sizes, k_coef_pack and k_coef_idct: what a block's record takes, how it
+// and its table entry are written, and how a lane gets its block back, checked.  Everything else is shared, and where a
+// shared kernel needs the table's size or a region's bounds it takes the format's number.  k_coef_idct asks in two steps,
+// find (the table; for the wide format also the header) and expand, with block_place between them as it always stood.
+struct WideRecords {
+    static constexpr int kFormat = RK_JPEG_COEF_WIDE;
+    typedef unsigned long long Shape;
+    static __device__ __forceinline__ Shape shape_of(const short* coef) { return rkjpeg::coef_header_of(coef); }
+    static __device__ __forceinline__ int bytes_of(Shape header) { return rkjpeg::coef_record_bytes(header); }
+    // offs: the frame's row of block_off
+    static __device__ __forceinline__ bool put_entry(RegionDst& dst, const rkjpeg::Geometry&, long long b, long long at, const unsigned*) {
+        dst.put16(4 * b, (unsigned)at & 0xFFFFu);
+        dst.put16(4 * b + 2, (unsigned)(at >> 16) & 0xFFFFu);
+        return true;
+    }
+    static __device__ __forceinline__ void pack(const short* coef, Shape header, RegionDst& dst, long long at) {
+        rkjpeg::coef_pack_block(coef, header, dst, at);
+    }
+    struct Where {          // of a block that find() accepted
+        long long at;
+        unsigned long long header;
+    };
+    // the table and the header: everything the wide format checks
+    static __device__ __forceinline__ bool find(RegionSrc& src, long long len, const rkjpeg::Geometry& g, long long b, Where* w) {
+        return rkjpeg::coef_block_ok(src, len, g, b, &w->at, &w->header);
+    }
+    static __device__ __forceinline__ bool expand(RegionSrc& src, const Where& w, short* coef) {
+        rkjpeg::coef_expand_block(src, w.at, w.header, coef);
+        return true;
+    }
+};
+
+struct DenseRecords {
+    static constexpr int kFormat = RK_JPEG_COEF_DENSE;
+    typedef rkjpeg::DenseShape Shape;
+    static __device__ __forceinline__ Shape shape_of(const short* coef) { return rkjpeg::dense_shape_of(coef); }
+    static __device__ __forceinline__ int bytes_of(const Shape& s) { return rkjpeg::dense_record_bytes(s); }
+    // base[g] = the start of the group's first record, from the same row of block_off; rel[b] = the distance from it
+    static __device__ __forceinline__ bool put_entry(RegionDst& dst, const rkjpeg::Geometry& g, long long b, long long at,
+                                                     const unsigned* offs) {
+        const long long base = offs[b & ~(long long)(rkjpeg::kDenseGroup - 1)];
+        if (at < base || at - base > 0xFFFF) return false;
+        if ((b & (rkjpeg::kDenseGroup - 1)) == 0) {
+            dst.put16(4 * (b / rkjpeg::kDenseGroup), (unsigned)base & 0xFFFFu);
+            dst.put16(4 * (b / rkjpeg::kDenseGroup) + 2, (unsigned)(base >> 16) & 0xFFFFu);
+        }
+        dst.put16(4 * rkjpeg::dense_groups(g) + 2 * b, (unsigned)(at - base));
+        return true;
+    }
+    static __device__ __forceinline__ void pack(const short* coef, const Shape& s, RegionDst& dst, long long at) {
+        rkjpeg::dense_pack_block(coef, s, dst, at);
+    }
+    struct Where {
+        long long at;
+        int span;
+    };
+    // the table alone gives the span; the record is checked against it as it is expanded
+    static __device__ __forceinline__ bool find(RegionSrc& src, long long len, const rkjpeg::Geometry& g, long long b, Where* w) {
+        return rkjpeg::dense_block_span(src, len, g, b, &w->at, &w->span);
+    }
+    static __device__ __forceinline__ bool expand(RegionSrc& src, const Where& w, short* coef) {
+        return rkjpeg::dense_expand_block(src, w.at, w.span, coef);
+    }
 };
 
 __device__ __forceinline__ long long frame_blocks(const rk_jpeg_frame& f) {
@@ -525,6 +600,7 @@ __device__ __forceinline__ void load_block(const unsigned char* __restrict__ bas
     for (int k = 0; k < 8; ++k) reinterpret_cast<uint4*>(coef)[k] = src[k];
 }
 
+template <class Records>
 __global__ __launch_bounds__(kBlock) void k_coef_block_sizes(const rk_jpeg_frame* __restrict__ frames,
                                                              const unsigned char* __restrict__ ws, const int* __restrict__ status,
                                                              const long long* __restrict__ first_block,
@@ -538,7 +614,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_block_sizes(const rk_jpeg_frame
     for (long long b = (long long)blockIdx.y * kBlock + threadIdx.x; b < g.nblocks; b += (long long)kBlock * gridDim.y) {
         alignas(16) short coef[64];
         load_block(base, b, coef);
-        out[b] = (unsigned)rkjpeg::coef_record_bytes(rkjpeg::coef_header_of(coef));
+        out[b] = (unsigned)Records::bytes_of(Records::shape_of(coef));
     }
 }
 
@@ -546,7 +622,8 @@ __global__ __launch_bounds__(kBlock) void k_coef_block_sizes(const rk_jpeg_frame
 // region's length, 0 for a frame with a code.  At most 12.6 M blocks of 136 bytes: below 2^32.
 __global__ __launch_bounds__(kBlock) void k_coef_frame_scan(const rk_jpeg_frame* __restrict__ frames, const int* __restrict__ status,
                                                             const long long* __restrict__ first_block,
-                                                            unsigned* __restrict__ block_off, long long* __restrict__ region_off) {
+                                                            unsigned* __restrict__ block_off, long long* __restrict__ region_off,
+                                                            int format) {
     __shared__ long long part[kBlock];
     const int i = blockIdx.x, t = threadIdx.x;
     if (status[i] != RK_JPEG_OK) {                      // uniform
@@ -562,7 +639,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_frame_scan(const rk_jpeg_frame*
     for (long long b = lo; b < hi; ++b) sum += mine[b];
     part[t] = sum;
     __syncthreads();
-    long long at = rkjpeg::coef_table_bytes(g);
+    long long at = rkjpeg::coef_table_bytes_as(format, g);
     for (int k = 0; k < t; ++k) at += part[k];
     for (long long b = lo; b < hi; ++b) {
         const unsigned bytes = mine[b];
@@ -591,6 +668,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_region_scan(long long* __restri
     if (t == kBlock - 1) region_off[n] = at;
 }
 
+template <class Records>
 __global__ __launch_bounds__(kBlock) void k_coef_pack(const rk_jpeg_frame* __restrict__ frames, const unsigned char* __restrict__ ws,
                                                       const int* __restrict__ status, const unsigned* __restrict__ block_off,
                                                       long long block_cap, const long long* __restrict__ first_block,
@@ -601,18 +679,17 @@ __global__ __launch_bounds__(kBlock) void k_coef_pack(const rk_jpeg_frame* __res
     rkjpeg::Geometry g;
     rkjpeg::geometry(frames[i], g);
     const long long lo = region_off[i], hi = region_off[i + 1], fb = first_block[i];
-    if (!rkjpeg::coef_region_ok(lo, hi, blob_bytes, g) || fb < 0 || fb > block_cap - g.nblocks) return;
+    if (!rkjpeg::coef_region_ok_as(Records::kFormat, lo, hi, blob_bytes, g) || fb < 0 || fb > block_cap - g.nblocks) return;
     const unsigned char* base = ws + reinterpret_cast<const long long*>(ws)[i];
     RegionDst dst{blob + lo};
     for (long long b = (long long)blockIdx.y * kBlock + threadIdx.x; b < g.nblocks; b += (long long)kBlock * gridDim.y) {
         alignas(16) short coef[64];
         load_block(base, b, coef);
-        const unsigned long long header = rkjpeg::coef_header_of(coef);
+        const typename Records::Shape shape = Records::shape_of(coef);
         const long long at = block_off[fb + b];
-        if (at < rkjpeg::coef_table_bytes(g) || (at & 1) || at > hi - lo - rkjpeg::coef_record_bytes(header)) continue;
-        dst.put16(4 * b, (unsigned)at & 0xFFFFu);
-        dst.put16(4 * b + 2, (unsigned)(at >> 16) & 0xFFFFu);
-        rkjpeg::coef_pack_block(coef, header, dst, at);
+        if (at < rkjpeg::coef_table_bytes_as(Records::kFormat, g) || (at & 1) || at > hi - lo - Records::bytes_of(shape)) continue;
+        if (!Records::put_entry(dst, g, b, at, block_off + fb)) continue;
+        Records::pack(coef, shape, dst, at);
     }
 }
 
@@ -624,7 +701,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_plan(const rk_jpeg_frame* __res
                                                       int nq, const int* __restrict__ pick, const int* __restrict__ build_status,
                                                       const long long* __restrict__ region_off, long long blob_bytes,
                                                       long long* __restrict__ offsets, long long workspace_bytes,
-                                                      int* __restrict__ flag, int* __restrict__ status) {
+                                                      int* __restrict__ flag, int* __restrict__ status, int format) {
     __shared__ long long part[kBlock];
     const int t = threadIdx.x, per = (m + kBlock - 1) / kBlock;
     const int lo = min(m, t * per), hi = min(m, lo + per);
@@ -644,7 +721,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_plan(const rk_jpeg_frame* __res
         if (rc == RK_JPEG_OK) {                         // a pick outside the set is a zero record and was refused above
             const int p = pick[j];
             rc = build_status[p];
-            if (rc == RK_JPEG_OK && !rkjpeg::coef_region_ok(region_off[p], region_off[p + 1], blob_bytes, g)) rc = RK_JPEG_BAD_INDEX;
+            if (rc == RK_JPEG_OK && !rkjpeg::coef_region_ok_as(format, region_off[p], region_off[p + 1], blob_bytes, g)) rc = RK_JPEG_BAD_INDEX;
         }
         flag[j] = 0;
         status[j] = rc;
@@ -652,6 +729,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_plan(const rk_jpeg_frame* __res
     if (t == kBlock - 1) offsets[m] = at;
 }
 
+template <class Records>
 __global__ __launch_bounds__(kBlock) void k_coef_idct(const rk_jpeg_frame* __restrict__ gathered,
                                                       const unsigned short* __restrict__ qtabs,
                                                       const unsigned char* __restrict__ blob, const long long* __restrict__ region_off,
@@ -667,9 +745,8 @@ __global__ __launch_bounds__(kBlock) void k_coef_idct(const rk_jpeg_frame* __res
     RegionSrc src{blob + lo};
     unsigned char* base = ws + reinterpret_cast<const long long*>(ws)[j];
     for (long long b = (long long)blockIdx.y * kBlock + threadIdx.x; b < g.nblocks; b += (long long)kBlock * gridDim.y) {
-        long long at;
-        unsigned long long header;
-        if (!rkjpeg::coef_block_ok(src, len, g, b, &at, &header)) {
+        typename Records::Where where;
+        if (!Records::find(src, len, g, b, &where)) {
             flag[j] = 1;                                // the same word from every lane that refuses; k_coef_status reads it
             continue;
         }
@@ -677,7 +754,10 @@ __global__ __launch_bounds__(kBlock) void k_coef_idct(const rk_jpeg_frame* __res
         long long off;
         rkjpeg::block_place(g, b, &comp, &off, &stride);
         alignas(16) short coef[64];
-        rkjpeg::coef_expand_block(src, at, header, coef);
+        if (!Records::expand(src, where, coef)) {       // the dense record did not fill its span (the wide one cannot fail here)
+            flag[j] = 1;
+            continue;
+        }
         const int qi = comp == 0 ? f.quant[0] : (comp == 1 ? f.quant[1] : f.quant[2]);
         const long long plane = comp == 0 ? g.plane_off[0] : (comp == 1 ? g.plane_off[1] : g.plane_off[2]);
         rkjpeg::idct_islow(coef, qtabs + (long long)qi * 64, base + plane + off, stride);
@@ -839,15 +919,15 @@ int rk_jpeg_decode_indexed_u8(const unsigned char* streams, long long stream_byt
     return launch_status();
 }
 
-int rk_jpeg_coef_sizes(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
-                       const rk_jpeg_huff* htabs, int nq, int nh, int n, const rk_jpeg_entry* entries, long long n_entries,
-                       const long long* entry_off, const int* seg_mcus, const int* build_status, int max_segments,
-                       void* workspace, size_t workspace_bytes, int* status, unsigned* block_off, long long block_cap,
-                       long long* first_block, long long* region_off, rk_stream_t stream) {
+int rk_jpeg_coef_sizes_as(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                          const rk_jpeg_huff* htabs, int nq, int nh, int n, const rk_jpeg_entry* entries, long long n_entries,
+                          const long long* entry_off, const int* seg_mcus, const int* build_status, int max_segments,
+                          void* workspace, size_t workspace_bytes, int* status, unsigned* block_off, long long block_cap,
+                          long long* first_block, long long* region_off, rk_stream_t stream, int record_format) {
     using namespace rk;
     if (any_null({streams, frames, htabs, status, block_off, first_block, region_off})) return RK_ERR_NULL_POINTER;
     if (entries && any_null({entry_off, seg_mcus, build_status})) return RK_ERR_NULL_POINTER;
-    if (!counts_ok({n, nq, nh, max_segments}) || !sizes_ok({stream_bytes, n_entries, block_cap}) ||
+    if (!rkjpeg::coef_format_ok(record_format) || !counts_ok({n, nq, nh, max_segments}) || !sizes_ok({stream_bytes, n_entries, block_cap}) ||
         !aligned(8, {frames, entries, entry_off, first_block, region_off}) ||
         !aligned(4, {htabs, status, seg_mcus, build_status, block_off}))
         return RK_ERR_BAD_DIMS;
@@ -873,27 +953,60 @@ int rk_jpeg_coef_sizes(const unsigned char* streams, long long stream_bytes, con
         hipLaunchKernelGGL(k_jpeg_entropy, dim3(n), dim3(kWave), 0, s, streams, frames, htabs, ws, status);
     }
     hipLaunchKernelGGL(k_coef_blocks, dim3(1), dim3(kBlock), 0, s, frames, n, block_cap, first_block, status);
-    hipLaunchKernelGGL(k_coef_block_sizes, dim3(n, kIdctSlices), dim3(kBlock), 0, s, frames, ws, status, first_block, block_off);
-    hipLaunchKernelGGL(k_coef_frame_scan, dim3(n), dim3(kBlock), 0, s, frames, status, first_block, block_off, region_off);
+    const auto sizes = record_format == RK_JPEG_COEF_DENSE ? k_coef_block_sizes<DenseRecords> : k_coef_block_sizes<WideRecords>;
+    hipLaunchKernelGGL(sizes, dim3(n, kIdctSlices), dim3(kBlock), 0, s, frames, ws, status, first_block, block_off);
+    hipLaunchKernelGGL(k_coef_frame_scan, dim3(n), dim3(kBlock), 0, s, frames, status, first_block, block_off, region_off,
+                       record_format);
     hipLaunchKernelGGL(k_coef_region_scan, dim3(1), dim3(kBlock), 0, s, region_off, n);
     hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, n);
+    return launch_status();
+}
+
+int rk_jpeg_coef_sizes(const unsigned char* streams, long long stream_bytes, const rk_jpeg_frame* frames,
+                       const rk_jpeg_huff* htabs, int nq, int nh, int n, const rk_jpeg_entry* entries, long long n_entries,
+                       const long long* entry_off, const int* seg_mcus, const int* build_status, int max_segments,
+                       void* workspace, size_t workspace_bytes, int* status, unsigned* block_off, long long block_cap,
+                       long long* first_block, long long* region_off, rk_stream_t stream) {
+    return rk_jpeg_coef_sizes_as(streams, stream_bytes, frames, htabs, nq, nh, n, entries, n_entries, entry_off, seg_mcus,
+                                 build_status, max_segments, workspace, workspace_bytes, status, block_off, block_cap,
+                                 first_block, region_off, stream, RK_JPEG_COEF_WIDE);
+}
+
+int rk_jpeg_coef_pack_as(const rk_jpeg_frame* frames, int n, int max_segments, const void* workspace, size_t workspace_bytes,
+                         const int* status, const unsigned* block_off, long long block_cap, const long long* first_block,
+                         const long long* region_off, unsigned char* blob, long long blob_bytes, rk_stream_t stream,
+                         int record_format) {
+    using namespace rk;
+    if (any_null({frames, status, block_off, first_block, region_off, blob})) return RK_ERR_NULL_POINTER;
+    if (!rkjpeg::coef_format_ok(record_format) || !counts_ok({n, max_segments}) || !sizes_ok({block_cap, blob_bytes}) ||
+        !aligned(8, {frames, first_block, region_off}) || !aligned(4, {status, block_off}) || !aligned(2, {blob}))
+        return RK_ERR_BAD_DIMS;
+    const long long head = rkjpeg::indexed_head_bytes(n, max_segments);
+    if (!workspace_ok(workspace, workspace_bytes, head + rkjpeg::offset_table_bytes(n))) return RK_ERR_WORKSPACE;
+    const unsigned char* ws = static_cast<const unsigned char*>(workspace) + head;
+    const auto pack = record_format == RK_JPEG_COEF_DENSE ? k_coef_pack<DenseRecords> : k_coef_pack<WideRecords>;
+    hipLaunchKernelGGL(pack, dim3(n, kIdctSlices), dim3(kBlock), 0, (hipStream_t)stream, frames, ws, status, block_off, block_cap,
+                       first_block, region_off, blob, blob_bytes);
     return launch_status();
 }
 
 int rk_jpeg_coef_pack(const rk_jpeg_frame* frames, int n, int max_segments, const void* workspace, size_t workspace_bytes,
                       const int* status, const unsigned* block_off, long long block_cap, const long long* first_block,
                       const long long* region_off, unsigned char* blob, long long blob_bytes, rk_stream_t stream) {
-    using namespace rk;
-    if (any_null({frames, status, block_off, first_block, region_off, blob})) return RK_ERR_NULL_POINTER;
-    if (!counts_ok({n, max_segments}) || !sizes_ok({block_cap, blob_bytes}) || !aligned(8, {frames, first_block, region_off}) ||
-        !aligned(4, {status, block_off}) || !aligned(2, {blob}))
-        return RK_ERR_BAD_DIMS;
-    const long long head = rkjpeg::indexed_head_bytes(n, max_segments);
-    if (!workspace_ok(workspace, workspace_bytes, head + rkjpeg::offset_table_bytes(n))) return RK_ERR_WORKSPACE;
-    const unsigned char* ws = static_cast<const unsigned char*>(workspace) + head;
-    hipLaunchKernelGGL(k_coef_pack, dim3(n, kIdctSlices), dim3(kBlock), 0, (hipStream_t)stream, frames, ws, status, block_off,
-                       block_cap, first_block, region_off, blob, blob_bytes);
-    return launch_status();
+    return rk_jpeg_coef_pack_as(frames, n, max_segments, workspace, workspace_bytes, status, block_off, block_cap, first_block,
+                                region_off, blob, blob_bytes, stream, RK_JPEG_COEF_WIDE);
+}
+
+int rk_jpeg_coef_region_bounds(int record_format, long long nblocks, long long* min_bytes, long long* max_bytes) {
+    if (!min_bytes || !max_bytes) return RK_ERR_NULL_POINTER;
+    if (!rkjpeg::coef_format_ok(record_format) || nblocks < 1) return RK_ERR_BAD_DIMS;
+    rkjpeg::Geometry g = {};
+    g.nblocks = nblocks;
+    const bool dense = record_format == RK_JPEG_COEF_DENSE;
+    const long long table = rkjpeg::coef_table_bytes_as(record_format, g);
+    *min_bytes = table + nblocks * (dense ? rkjpeg::kDenseRecordMin : rkjpeg::kCoefRecordMin);
+    *max_bytes = table + nblocks * (dense ? rkjpeg::kDenseRecordMax : rkjpeg::kCoefRecordMax);
+    return RK_OK;
 }
 
 size_t rk_jpeg_coef_workspace_bytes(const rk_jpeg_frame* frames_host, int n, const int* pick_host, int m) {
@@ -904,13 +1017,13 @@ size_t rk_jpeg_coef_workspace_bytes(const rk_jpeg_frame* frames_host, int n, con
     return (size_t)total;
 }
 
-int rk_jpeg_decode_coef_u8(const unsigned char* blob, long long blob_bytes, const rk_jpeg_frame* frames,
-                           const unsigned short* qtabs, int nq, int n, const long long* region_off, const int* build_status,
-                           const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
-                           void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream) {
+int rk_jpeg_decode_coef_as_u8(const unsigned char* blob, long long blob_bytes, const rk_jpeg_frame* frames,
+                              const unsigned short* qtabs, int nq, int n, const long long* region_off, const int* build_status,
+                              const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
+                              void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream, int record_format) {
     using namespace rk;
     if (any_null({blob, frames, qtabs, region_off, build_status, pick, rgb_off, rgb, status})) return RK_ERR_NULL_POINTER;
-    if (n < 1 || !counts_ok({nq, m}) || !sizes_ok({blob_bytes, rgb_bytes}) || !aligned(8, {frames, region_off, rgb_off}) ||
+    if (!rkjpeg::coef_format_ok(record_format) || n < 1 || !counts_ok({nq, m}) || !sizes_ok({blob_bytes, rgb_bytes}) || !aligned(8, {frames, region_off, rgb_off}) ||
         !aligned(4, {status, build_status, pick}) || !aligned(2, {qtabs, blob}))
         return RK_ERR_BAD_DIMS;
     const long long head = rkjpeg::coef_head_bytes(m);
@@ -923,12 +1036,21 @@ int rk_jpeg_decode_coef_u8(const unsigned char* blob, long long blob_bytes, cons
     const int groups = (m + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_jpeg_gather, dim3(groups), dim3(kBlock), 0, s, frames, n, pick, rgb_off, m, gathered);
     hipLaunchKernelGGL(k_coef_plan, dim3(1), dim3(kBlock), 0, s, gathered, m, rgb_bytes, nq, pick, build_status, region_off,
-                       blob_bytes, reinterpret_cast<long long*>(ws), (long long)workspace_bytes - head, flag, status);
-    hipLaunchKernelGGL(k_coef_idct, dim3(m, kIdctSlices), dim3(kBlock), 0, s, gathered, qtabs, blob, region_off, pick, ws, status, flag);
+                       blob_bytes, reinterpret_cast<long long*>(ws), (long long)workspace_bytes - head, flag, status, record_format);
+    const auto idct = record_format == RK_JPEG_COEF_DENSE ? k_coef_idct<DenseRecords> : k_coef_idct<WideRecords>;
+    hipLaunchKernelGGL(idct, dim3(m, kIdctSlices), dim3(kBlock), 0, s, gathered, qtabs, blob, region_off, pick, ws, status, flag);
     hipLaunchKernelGGL(k_coef_status, dim3(groups), dim3(kBlock), 0, s, flag, m, status);
     hipLaunchKernelGGL(k_jpeg_colour, dim3(m, kColourSlices), dim3(kBlock), 0, s, gathered, ws, status, rgb, rgb_bytes);
     hipLaunchKernelGGL(k_jpeg_count, dim3(1), dim3(kBlock), 0, s, status, m);
     return launch_status();
+}
+
+int rk_jpeg_decode_coef_u8(const unsigned char* blob, long long blob_bytes, const rk_jpeg_frame* frames,
+                           const unsigned short* qtabs, int nq, int n, const long long* region_off, const int* build_status,
+                           const int* pick, const long long* rgb_off, int m, unsigned char* rgb, long long rgb_bytes,
+                           void* workspace, size_t workspace_bytes, int* status, rk_stream_t stream) {
+    return rk_jpeg_decode_coef_as_u8(blob, blob_bytes, frames, qtabs, nq, n, region_off, build_status, pick, rgb_off, m, rgb,
+                                     rgb_bytes, workspace, workspace_bytes, status, stream, RK_JPEG_COEF_WIDE);
 }
 
 }  // extern "C"

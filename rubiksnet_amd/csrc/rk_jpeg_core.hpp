@@ -2,8 +2,8 @@
 // geometry, bit reader, Huffman step, one scan's entropy decode -- whole, or a span of MCUs resumed at a recorded entry,
 // the walk that records those entries, and the same entries from many short walks in lock-step rounds -- jidctint's ISLOW
 // IDCT, the packed form of a frame's coefficients with its checks, fancy upsampling and YCbCr -> RGB.  The kernels only
-// distribute this code over lanes; tests/jpeg_core_main.cpp, tests/jpeg_index_main.cpp, tests/jpeg_chunked_main.cpp and
-// tests/jpeg_coef_main.cpp compile the same text for the CPU under AddressSanitizer /
+// distribute this code over lanes; tests/jpeg_core_main.cpp, tests/jpeg_index_main.cpp, tests/jpeg_chunked_main.cpp,
+// tests/jpeg_coef_main.cpp and tests/jpeg_dense_main.cpp compile the same text for the CPU under AddressSanitizer /
 // UBSan, which is the bounds proof for the kernels' logic.  That holds for everything in this file, the chunked build's
 // per-frame driver included: its phases are here, and what rk_jpeg.hip adds to them is barriers.  It does not hold for
 // what only rk_jpeg.hip has: the stream sources, the lane sink, the plan kernels' sums and the launch geometry.
@@ -908,6 +908,212 @@ RKJ_HD bool coef_block_ok(Src& src, long long region_len, const Geometry& g, lon
     *at = off;
     *header = h;
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------ dense records
+// The second record format of the same packed set (RK_JPEG_COEF_DENSE; the one above is RK_JPEG_COEF_WIDE and stays as it
+// is).  Video frames have, per block, one to three large low-frequency values and some 25 small ones, so the value class
+// is chosen per COEFFICIENT: a 4-bit nibble each, and a byte or a word only for the few that do not fit one.  One
+// frame's region, little endian, every record on a 2-byte boundary, no padding between regions:
+//
+//   uint32 base[G]         G = ceil(nblocks / 64); read and written as two 16-bit halves, low half first
+//   uint16 rel[nblocks]    block b's record starts base[b / 64] + rel[b] bytes from the region's start (blocks in
+//                          block_place's order, MCU padding blocks included).  The packer writes base[g] = the start of
+//                          record 64 g, so rel[64 g] = 0 and rel <= 63 * 130.
+//   records, back to back, in block order: the first at 4 G + 2 nblocks, the last one ends the region
+//
+//   ordinary record
+//     uint8  tag            bits 0-5 `last`: the zigzag position of the last non-zero AC (0: no AC); bits 6-7 the class
+//     int16  DC             (at an odd offset: read and written as bytes)
+//     ceil(last / 8) mask bytes: bit j of the mask = the AC at zigzag position j + 1 is not zero
+//     ceil(n / 2) bytes of nibbles, one per non-zero AC in zigzag order, low nibble first: the value in 4-bit two's
+//                           complement where it lies in -7 .. 7, 0x8 = escaped (a nibble of 0 names no value)
+//     the e escaped values in order: int8 each in class 0, int16 each in class 1 (used when one of them leaves int8)
+//     one zero byte where that leaves an odd count:  roundup2(3 + ceil(last / 8) + ceil(n / 2) + e w), 4 .. 130 bytes
+//   raw record (class 2), for a block whose ordinary record would exceed 130 bytes
+//     tag 0x80, a zero byte, int16[64] in natural order: 130 bytes
+//
+// A reader takes a record's SPAN -- [its start, the next record's start), the region's end for the last -- from the
+// table alone (dense_block_span), checks every read of the record against that span before it makes it, and refuses a
+// record whose own length, from its tag, mask, nibbles and class, is not exactly the span (dense_expand_block).  The
+// loops are bounded by the 63 positions and the block count.
+// Src and Dst as above.
+constexpr int kDenseRecordMin = 4, kDenseRecordMax = 130, kDenseGroup = 64;
+
+RKJ_HD long long dense_groups(const Geometry& g) { return (g.nblocks + kDenseGroup - 1) / kDenseGroup; }
+RKJ_HD long long dense_table_bytes(const Geometry& g) { return 4 * dense_groups(g) + 2 * g.nblocks; }
+
+struct DenseShape {         // of a block's 64 coefficients: what its record's length follows from
+    int last, n, e;         // the last non-zero AC's zigzag position, the non-zero ACs, those outside -7 .. 7
+    bool wide, raw;         // an escaped value leaves int8; the ordinary record would exceed kDenseRecordMax
+};
+
+RKJ_HD int dense_ordinary_bytes(int last, int n, int e, bool wide) {
+    return (3 + ((last + 7) >> 3) + ((n + 1) >> 1) + e * (wide ? 2 : 1) + 1) & ~1;
+}
+
+RKJ_HD DenseShape dense_shape_of(const short* coef) {
+    DenseShape s = {0, 0, 0, false, false};
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        const int v = coef[natural_of(k)];
+        if (v != 0) {
+            s.last = k;
+            ++s.n;
+        }
+        if (v < -7 || v > 7) ++s.e;
+        s.wide = s.wide || v < -128 || v > 127;
+    }
+    s.raw = dense_ordinary_bytes(s.last, s.n, s.e, s.wide) > kDenseRecordMax;
+    return s;
+}
+RKJ_HD int dense_record_bytes(const DenseShape& s) {
+    return s.raw ? kDenseRecordMax : dense_ordinary_bytes(s.last, s.n, s.e, s.wide);
+}
+
+// Writes the block's record at `at` (even); dense_record_bytes(s) bytes, every one of them.
+template <class Dst>
+RKJ_HD void dense_pack_block(const short* coef, const DenseShape& s, Dst& dst, long long at) {
+    if (s.raw) {
+        dst.put16(at, 0x0080u);
+#pragma unroll
+        for (int k = 0; k < 64; ++k) dst.put16(at + 2 + 2 * k, (unsigned)coef[k] & 0xFFFFu);
+        return;
+    }
+    dst.put8(at, s.last | (s.wide ? 0x40 : 0));
+    dst.put8(at + 1, coef[0] & 0xFF);
+    dst.put8(at + 2, (coef[0] >> 8) & 0xFF);
+    const int mb = (s.last + 7) >> 3;
+    long long np = at + 3 + mb, ep = np + ((s.n + 1) >> 1);
+    unsigned mbyte = 0, nbyte = 0;
+    int c = 0;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        const int v = coef[natural_of(k)];
+        if (v != 0) {
+            mbyte |= 1u << ((k - 1) & 7);
+            const bool small = v >= -7 && v <= 7;
+            nbyte |= (small ? (unsigned)v & 15u : 8u) << (4 * (c & 1));
+            if (c & 1) {
+                dst.put8(np++, (int)nbyte);
+                nbyte = 0;
+            }
+            ++c;
+            if (!small) {
+                dst.put8(ep++, v & 0xFF);
+                if (s.wide) dst.put8(ep++, (v >> 8) & 0xFF);
+            }
+        }
+        if ((k & 7) == 0 || k == 63) {                  // positions 8 i + 1 .. 8 i + 8 are mask byte i
+            if (((k - 1) >> 3) < mb) dst.put8(at + 3 + ((k - 1) >> 3), (int)mbyte);
+            mbyte = 0;
+        }
+    }
+    if (c & 1) dst.put8(np, (int)nbyte);
+    if ((ep - at) & 1) dst.put8(ep, 0);
+}
+
+// May bytes [lo, hi) of a blob of blob_bytes be frame g's dense region?  Inside the blob, both ends on a 2-byte boundary,
+// and between the table plus the smallest and the table plus the largest record of every block.
+RKJ_HD bool dense_region_ok(long long lo, long long hi, long long blob_bytes, const Geometry& g) {
+    if (lo < 0 || hi < lo || hi > blob_bytes || (lo & 1) || (hi & 1)) return false;
+    const long long len = hi - lo, table = dense_table_bytes(g);
+    return len >= table + g.nblocks * kDenseRecordMin && len <= table + g.nblocks * kDenseRecordMax;
+}
+
+RKJ_HD long long dense_start_of(unsigned base_lo, unsigned base_hi, unsigned rel) { return coef_offset_of(base_lo, base_hi) + (long long)(rel & 0xFFFFu); }
+
+// Block b of a region that passed dense_region_ok, from the table alone: its record's start -- behind the table, even,
+// with room for the smallest record; exactly behind the table for block 0 -- and its span up to the next record's start
+// (the region's end for the last block), 4 .. 130 bytes inside the region.  true: [*at, *at + *span) is the record's.
+template <class Src>
+RKJ_HD bool dense_block_span(Src& src, long long region_len, const Geometry& g, long long b, long long* at, int* span) {
+    const long long rel0 = 4 * dense_groups(g), table = dense_table_bytes(g);
+    const long long gb = b / kDenseGroup, gn = (b + 1) / kDenseGroup;
+    const long long off = dense_start_of(src.u16(4 * gb), src.u16(4 * gb + 2), src.u16(rel0 + 2 * b));
+    const long long end = b + 1 < g.nblocks ? dense_start_of(src.u16(4 * gn), src.u16(4 * gn + 2), src.u16(rel0 + 2 * b + 2)) : region_len;
+    if ((off & 1) || off < table || off > region_len - kDenseRecordMin) return false;
+    if (b == 0 && off != table) return false;
+    if (end > region_len || end - off < kDenseRecordMin || end - off > kDenseRecordMax) return false;
+    *at = off;
+    *span = (int)(end - off);
+    return true;
+}
+
+// The record in [at, at + span) -- dense_block_span's: at even, span even -- back into 64 coefficients (natural order),
+// checked as it is read: false for class 3, a raw record with last != 0 or another span than 130, a mask whose bit
+// `last` is clear or that has a bit above it, a nibble of 0 for a coefficient the mask names, a read that would leave
+// the span, and a record whose own length is not the span; coef is then not to be used.  No read is made before it is
+// known to lie in the span.  The mask sits in one 64-bit word; the nibbles come out of a 32-bit window that is refilled
+// every eighth nibble from an address that follows from the count of nibbles taken, which the mask gives, so no load
+// but an escaped value's waits for loaded data; the loop is unrolled with every index a constant, so that on the
+// device coef[] stays in registers.
+template <class Src>
+RKJ_HD bool dense_expand_block(Src& src, long long at, int span, short* coef) {
+    const unsigned w0 = src.u16(at), w1 = src.u16(at + 2);              // span >= 4
+    const int last = (int)(w0 & 63u), cls = (int)((w0 >> 6) & 3u);
+    if (cls == 2) {
+        if (last != 0 || span != kDenseRecordMax) return false;
+        coef[0] = (short)w1;
+#pragma unroll
+        for (int k = 1; k < 64; ++k) coef[k] = (short)src.u16(at + 2 + 2 * k);
+        return true;
+    }
+    const int mb = (last + 7) >> 3, w = cls == 1 ? 2 : 1;
+    if (cls == 3 || 3 + mb > span) return false;
+    coef[0] = (short)((w0 >> 8) | ((w1 & 0xFFu) << 8));
+    unsigned long long m = w1 >> 8;                                     // byte 3 of the record is mask byte 0
+#pragma unroll
+    for (int i = 0; i < 4; ++i)                                         // bytes 4 + 2 i, 5 + 2 i: mask bytes 1 + 2 i, 2 + 2 i
+        if (4 + 2 * i < 3 + mb) m |= (unsigned long long)(src.u16(at + 4 + 2 * i) & 0xFFFFu) << (8 + 16 * i);
+    if (mb < 8) m &= (1ull << (8 * mb)) - 1ull;
+    if (last > 0 && (m >> (last - 1)) != 1ull) return false;
+    const int n = __builtin_popcountll(m);
+    const int nib_at = 3 + mb;
+    int ep = nib_at + ((n + 1) >> 1);                                   // the escaped values' place
+    if (ep > span) return false;
+    const unsigned long long mask = m << 1;                             // bit k: zigzag position k
+    const int a0 = nib_at & ~1;
+    int c = (nib_at & 1) ? 2 : 0;                                       // nibbles from a0 on
+    unsigned win = 0;
+    if (a0 < span) win = src.u16(at + a0) & 0xFFFFu;
+    if (a0 + 2 < span) win |= (src.u16(at + a0 + 2) & 0xFFFFu) << 16;
+    bool bad = false;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        int v = 0;
+        if ((mask >> k) & 1) {
+            const unsigned nib = (win >> (4 * (c & 7))) & 15u;
+            ++c;
+            if ((c & 7) == 0) {
+                const int r = a0 + (c >> 1);
+                win = r < span ? src.u16(at + r) & 0xFFFFu : 0u;
+                if (r + 2 < span) win |= (src.u16(at + r + 2) & 0xFFFFu) << 16;
+            }
+            v = (int)(nib ^ 8u) - 8;
+            bad = bad || nib == 0;
+            if (nib == 8) {
+                v = 0;
+                if (ep + w <= span) {
+                    v = w == 2 ? (int)(short)((src.s8(at + ep) & 0xFF) | ((src.s8(at + ep + 1) & 0xFF) << 8)) : src.s8(at + ep);
+                } else {
+                    bad = true;
+                }
+                ep += w;
+            }
+        }
+        coef[natural_of(k)] = (short)v;
+    }
+    return !bad && ((ep + 1) & ~1) == span;
+}
+
+// The two formats by number, for what both share: the scans, the plan and the host's bounds.
+RKJ_HD bool coef_format_ok(int format) { return format == RK_JPEG_COEF_WIDE || format == RK_JPEG_COEF_DENSE; }
+RKJ_HD long long coef_table_bytes_as(int format, const Geometry& g) {
+    return format == RK_JPEG_COEF_DENSE ? dense_table_bytes(g) : coef_table_bytes(g);
+}
+RKJ_HD bool coef_region_ok_as(int format, long long lo, long long hi, long long blob_bytes, const Geometry& g) {
+    return format == RK_JPEG_COEF_DENSE ? dense_region_ok(lo, hi, blob_bytes, g) : coef_region_ok(lo, hi, blob_bytes, g);
 }
 
 // A record that is decoded from a packed region: its sizes, its output range, its quantisation tables and ws_end, the

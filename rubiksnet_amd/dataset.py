@@ -661,11 +661,14 @@ class DeviceFrameCache(_Feeder):
     shorter than "jpeg"'s, a footprint between the two others' (content decides: noisy frames pack poorly), and a
     construction that takes the transcode's time.  budget_bytes counts the packed blob, its tables, the records, the
     host-decoded frames, the batch buffers and, while the build runs, a slab's buffers; it is asked before every
-    allocation of the build.  A batch stays valid until the next one is asked for."""
+    allocation of the build.  coef_record="dense" (with resident="coef") keeps the denser records of
+    jpeg.build_coef(record="dense") -- a nibble per small AC value, about two thirds of the "wide" bytes on video frames
+    -- decoded by the same launch with another expansion per block; clips stay bit-identical.  A batch stays valid until
+    the next one is asked for."""
 
     def __init__(self, source, batch, split, device="cuda:0", dtype=torch.float32, size=224, views=1, box_fn=None, seed=0,
                  temporal_clips=None, shuffle=None, drop_last=False, flip_p=0.5, budget_bytes=4 << 30, resident="rgb",
-                 index_build="chain", slab_frames=256, **sampling):
+                 index_build="chain", slab_frames=256, coef_record="wide", **sampling):
         self.slab_frames = int(slab_frames)
         if resident not in ("rgb", "jpeg", "coef"):
             raise ValueError("resident must be 'rgb' or 'jpeg' or 'coef', got %r" % (resident,))
@@ -674,7 +677,12 @@ class DeviceFrameCache(_Feeder):
         if index_build == "chunked" and resident not in ("jpeg", "coef"):
             raise ValueError("index_build='chunked' builds the scan index of resident files: it goes with resident='jpeg' or "
                              "'coef', not %r" % (resident,))
-        self.index_build = index_build
+        if coef_record not in jpeg.COEF_RECORDS:
+            raise ValueError("coef_record must be 'wide' or 'dense', got %r" % (coef_record,))
+        if coef_record != "wide" and resident != "coef":
+            raise ValueError("coef_record=%r chooses the records of resident='coef': it does not go with resident=%r"
+                             % (coef_record, resident))
+        self.index_build, self.coef_record = index_build, coef_record
         if resident in ("jpeg", "coef") and not (isinstance(source, RubiksDataset) and source.decode == "device"):
             raise ValueError("resident=%r %s: it needs a RubiksDataset(..., decode='device'), not "
                              "%s" % (resident, "keeps the files' bytes" if resident == "jpeg" else "transcodes the files",
@@ -754,7 +762,8 @@ class DeviceFrameCache(_Feeder):
                                    "of %d bytes; raise budget_bytes or stream with FrameLoader"
                                    % (len(self.source), held + fallback, self.budget_bytes))
 
-        self.coef = jpeg.build_coef(res, self.device, method=self.index_build, slab_frames=self.slab_frames, admit=admit)
+        self.coef = jpeg.build_coef(res, self.device, method=self.index_build, slab_frames=self.slab_frames, admit=admit,
+                                    record=self.coef_record)
         n = self.coef.n
         self._fixed_bytes = self.coef.blob.numel() + n * 64 + self.coef.qtabs.numel() + (n + 1) * 12 + fallback
         self._fallback = torch.empty(fallback, dtype=torch.uint8, device=self.device)

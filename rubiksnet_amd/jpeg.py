@@ -31,6 +31,8 @@ A resident set can also be kept as what the Huffman stage leaves (dataset.Device
                          rk_jpeg_coef_pack): per block an offset, a 64-bit mask, the DC and the non-zero AC values
   launch_decode_coef     the per-batch launch (rk_jpeg_decode_coef_u8): no Huffman stage, the same IDCT on the same
                          coefficients; pick_tables as above
+  build_coef(record="dense") packs the second record format (a nibble per small AC value; include/rubiks_hip.h); the
+                         DeviceCoef remembers it and launch_decode_coef dispatches on it
 
 There is no CPU path: a missing library is an error (tests compare with Pillow).
 """
@@ -45,7 +47,8 @@ __all__ = ["JpegHeader", "parse_jpeg", "pack_jpeg_clips", "PackedJpeg", "decode_
            "ResidentJpeg", "pack_resident", "DeviceIndex", "build_index", "PickTables", "pick_tables",
            "frame_workspace_bytes", "indexed_workspace_bytes_for", "launch_decode_indexed", "chunked_workspace_bytes_for",
            "launch_build_index_chunked", "RowTables", "row_tables", "launch_decode_rows", "CHUNK_BYTES", "MAX_ROUNDS",
-           "MAX_CHUNKS", "DeviceCoef", "build_coef", "frame_plane_bytes", "coef_workspace_bytes_for", "launch_decode_coef"]
+           "MAX_CHUNKS", "DeviceCoef", "build_coef", "frame_plane_bytes", "coef_workspace_bytes_for", "launch_decode_coef",
+           "coef_region_bounds", "COEF_RECORDS"]
 
 MAX_SIDE = 16384
 STATUS_NAMES = ("ok", "bad record", "bad code", "run past 63", "truncated", "bad restart", "trailing data", "bad value",
@@ -636,9 +639,24 @@ DeviceCoef = collections.namedtuple("DeviceCoef", [
     "packed_bytes",     # bytes of all regions
     "file_bytes",       # bytes of the same frames' entropy-coded segments, what resident="jpeg" would keep of them
     "build_bytes",      # the most the build held on the device beside the blob and the tables (one slab's buffers)
-])
+    "record",           # "wide" or "dense": the record format of the blob (RK_JPEG_COEF_WIDE / RK_JPEG_COEF_DENSE)
+], defaults=("wide",))
 
 COEF_RECORD_MIN, COEF_RECORD_MAX = 10, 136
+COEF_DENSE_RECORD_MIN, COEF_DENSE_RECORD_MAX, COEF_DENSE_GROUP = 4, 130, 64
+COEF_RECORDS = {"wide": 0, "dense": 1}
+
+
+def coef_region_bounds(record, nblocks):
+    """(least, most) bytes of one frame's region of nblocks blocks in record format `record`, the table included
+    (rk_jpeg_coef_region_bounds, in Python)."""
+    if record not in COEF_RECORDS:
+        raise ValueError("record must be 'wide' or 'dense', got %r" % (record,))
+    nblocks = int(nblocks)
+    if record == "dense":
+        table = 4 * ((nblocks + COEF_DENSE_GROUP - 1) // COEF_DENSE_GROUP) + 2 * nblocks
+        return table + nblocks * COEF_DENSE_RECORD_MIN, table + nblocks * COEF_DENSE_RECORD_MAX
+    return nblocks * (4 + COEF_RECORD_MIN), nblocks * (4 + COEF_RECORD_MAX)
 
 
 def frame_plane_bytes(frames):
@@ -664,7 +682,8 @@ def _as_bytes(arr, device):
     return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).reshape(-1).copy()).to(device)
 
 
-def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk_bytes=256, max_rounds=32, admit=None):
+def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk_bytes=256, max_rounds=32, admit=None,
+               record="wide"):
     """A ResidentJpeg transcoded on the device into packed DCT coefficients (rk_jpeg_coef_sizes, rk_jpeg_coef_pack): every
     frame's Huffman code is undone once, here.  The set goes through in slabs of slab_frames frames: a slab's file bytes
     and records are uploaded, its entropy stage runs -- method="chain": one chain per frame; method="chunked": the scan
@@ -673,8 +692,10 @@ def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk
     then the slab's buffers are dropped, so the file bytes, the index entries and the 128-byte-per-block workspace never
     exist for more than one slab.  The blob is allocated once the first slab is measured, at that slab's bytes per frame
     for the whole set plus 3 % (and again, larger, should a later slab not fit).  admit(bytes): called before every
-    allocation with the bytes the build is about to hold on the device (the blob included); it may raise.  Returns a
-    DeviceCoef.  The host waits once per slab."""
+    allocation with the bytes the build is about to hold on the device (the blob included); it may raise.
+    record="dense" packs the denser records (rk_jpeg_coef_sizes_as / rk_jpeg_coef_pack_as with RK_JPEG_COEF_DENSE: a
+    nibble per small AC value, a byte or a word only for the few large ones, a table of half the size); the build is
+    otherwise the same and the DeviceCoef remembers its format.  Returns a DeviceCoef.  The host waits once per slab."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("build_coef runs on a GPU (no CPU path)")
@@ -684,6 +705,8 @@ def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk
         raise ValueError("slab_frames must be in [1, %d], got %r" % (MAX_LAUNCH, slab_frames))
     if method == "chunked":
         _check_chunking(chunk_bytes, max_rounds)
+    if record not in COEF_RECORDS:
+        raise ValueError("record must be 'wide' or 'dense', got %r" % (record,))
     from . import _native
     admit = admit or (lambda held: None)
     (frames_h, htabs_h, qtabs_h, streams_h), (n, nh, nq) = sections(resident.blob, resident.layout)
@@ -730,9 +753,9 @@ def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk
                                        max_rounds, torch.empty(build_ws_bytes, dtype=torch.uint8, device=device), build_status,
                                        route)
             index = (entries.data_ptr(), n_entries, entry_off.data_ptr(), seg_mcus.data_ptr(), build_status.data_ptr())
-        _native.launch("rk_jpeg_coef_sizes", device, streams.data_ptr(), streams.numel(), slab_d.data_ptr(), htabs.data_ptr(), nq,
+        _native.launch("rk_jpeg_coef_sizes_as", device, streams.data_ptr(), streams.numel(), slab_d.data_ptr(), htabs.data_ptr(), nq,
                        nh, k, *index, most, ws.data_ptr(), ws.numel(), part_status.data_ptr(), block_off.data_ptr(), cap,
-                       first_block.data_ptr(), rel.data_ptr())
+                       first_block.data_ptr(), rel.data_ptr(), after=(COEF_RECORDS[record],))
         total = int(rel[k].item())                      # the host waits here, once per slab
         if blob is None or done + total > room:
             # the blob is one allocation that the slabs fill in turn: its size is the first slab's bytes a frame carried over
@@ -746,8 +769,9 @@ def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk
             blob, room = grown, want
             del grown
         rel += done
-        _native.launch("rk_jpeg_coef_pack", device, slab_d.data_ptr(), k, most, ws.data_ptr(), ws.numel(), part_status.data_ptr(),
-                       block_off.data_ptr(), cap, first_block.data_ptr(), rel.data_ptr(), blob.data_ptr(), room)
+        _native.launch("rk_jpeg_coef_pack_as", device, slab_d.data_ptr(), k, most, ws.data_ptr(), ws.numel(), part_status.data_ptr(),
+                       block_off.data_ptr(), cap, first_block.data_ptr(), rel.data_ptr(), blob.data_ptr(), room,
+                       after=(COEF_RECORDS[record],))
         region_off[lo:hi + 1].copy_(rel)
         status[lo:hi].copy_(part_status[:k])
         status[n] += part_status[k]
@@ -757,12 +781,12 @@ def build_coef(resident, device="cuda:0", method="chain", slab_frames=256, chunk
     del htabs
     if blob is None:                                    # no frame at all: sixteen bytes that no region lies in
         blob = torch.zeros(16, dtype=torch.uint8, device=device)
-    return DeviceCoef(blob, region_off, frames, qtabs, n, nq, status, done, int(rec["stream_len"].sum()), most_held)
+    return DeviceCoef(blob, region_off, frames, qtabs, n, nq, status, done, int(rec["stream_len"].sum()), most_held, record)
 
 
 def launch_decode_coef(coef, pick, rgb_off, rgb, workspace, status):
-    """rk_jpeg_decode_coef_u8 on the current stream.  coef: a DeviceCoef; pick int32 [m], rgb_off int64 [m], rgb uint8
-    [rgb_bytes], workspace uint8 (16-byte aligned, coef_workspace_bytes_for), status int32 [m + 1]: device tensors.  Nothing
+    """rk_jpeg_decode_coef_as_u8, in the DeviceCoef's record format, on the current stream.  coef: a DeviceCoef; pick
+    int32 [m], rgb_off int64 [m], rgb uint8 [rgb_bytes], workspace uint8 (16-byte aligned, coef_workspace_bytes_for), status int32 [m + 1]: device tensors.  Nothing
     is allocated and the host does not wait."""
     from . import _native
     m = pick.numel()
@@ -770,10 +794,10 @@ def launch_decode_coef(coef, pick, rgb_off, rgb, workspace, status):
                     ("workspace", workspace, torch.uint8), ("status", status, torch.int32)))
     if rgb_off.numel() != m or status.numel() < m + 1:
         raise ValueError("pick [%d], rgb_off [%d], status [%d]: want m, m, m + 1" % (m, rgb_off.numel(), status.numel()))
-    _native.launch("rk_jpeg_decode_coef_u8", rgb.device, coef.blob.data_ptr(), coef.packed_bytes, coef.frames.data_ptr(),
+    _native.launch("rk_jpeg_decode_coef_as_u8", rgb.device, coef.blob.data_ptr(), coef.packed_bytes, coef.frames.data_ptr(),
                    coef.qtabs.data_ptr(), coef.nq, coef.n, coef.region_off.data_ptr(), coef.status.data_ptr(), pick.data_ptr(),
                    rgb_off.data_ptr(), m, rgb.data_ptr(), rgb.numel(), workspace.data_ptr(), workspace.numel(),
-                   status.data_ptr())
+                   status.data_ptr(), after=(COEF_RECORDS[coef.record],))
 
 
 # ------------------------------------------------------------------------------------------------- a streamed batch by rows
